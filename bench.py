@@ -1,6 +1,6 @@
 """Throughput benchmark: mel-frames/s of the Conformer-L encoder training step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config L15]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config L15] [--dump-outputs DIR] [--full]
     (N > 1: either under python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N, or plain
     `python bench.py --gpus N`, which starts that launcher itself as a child process; --gpus must equal the
     launcher's WORLD_SIZE, else the run exits 2)
@@ -12,9 +12,13 @@ step.  Forward + backward are captured once into a HIP graph and replayed (--eag
 Python every step); dropout masks still change every step (device step counter, cfm_rng_bind).  Inputs are synthetic 80-bin log-mel batches already resident in HBM
 (SURVEY.md §8d), weights random-init.  Weak scaling: B=32 utterances per GPU.
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel, measured
-live with HIP events on its launch stream over the timed region) and `cpu_baseline` (the CPU
-oracle, rank 0 at N=1 only, bounded sample).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the contract fields
+(`value`, `ms_per_step`, ...), the step's configuration and the non-finite-loss count the steps kept themselves.
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy (training_outputs; the inputs
+and initial weights are seeded, so two builds run with the same arguments compare output for output).
+--full adds everything that takes runs of its own after the timed steps: the `roofline*` entries (live kernel
+probes on replays of a second captured step), `ctc_head` (the head alone), `params_finite`, and `cpu_baseline`
+(the CPU oracle, rank 0 at N=1 only, bounded sample; --no-cpu-baseline leaves it out).
 """
 from __future__ import annotations
 
@@ -164,6 +168,8 @@ def run_nst(args, model, x, lens_i32, dev, cfg, rank, world):
         tt = torch.tensor([elapsed], device=dev)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         elapsed = tt.item()
+    if args.dump_outputs and rank == 0:     # the label pass's return: argmax ids, stripped labels (-1 padded), counts
+        dump_outputs(args.dump_outputs, {"ids": out[0], "labels": out[1], "label_counts": out[2]})
     fwd_pf, _ = algorithmic_flops_per_frame(L, d, H, ffn, K, T_in, model.T2, model.F2, rel=pos_enc == "rel", B=B)
     ms = 1000.0 * elapsed / args.steps
     value = B * T_in * world * args.steps / elapsed
@@ -489,8 +495,11 @@ class Harness:
 
     def __init__(self, cfg, dev, rank=0, world=1, *, dropout=0.1, fp8=False, specaug=False, dp_overlap=False,
                  chunk_layers=4,
-                 eager=False, no_optimizer=False, probe_inline=False, lr=2e-5, seed=1234, grad_bf16=False):
+                 eager=False, no_optimizer=False, probe_inline=False, lr=2e-5, seed=1234, grad_bf16=False,
+                 keep_logits=False):
         self.cfg = cfg
+        self.keep_logits = bool(keep_logits)         # --dump-outputs: hold the step's logits (static in the graph)
+        self.static_logits = None
         name, L, d, H, ffn, K, B, secs, pos_enc = cfg
         self.dev, self.rank, self.world = dev, rank, world
         self.eager = bool(eager)
@@ -558,8 +567,10 @@ class Harness:
 
     def fwd_bwd(self):
         self.rng.add_(1)
-        loss, _ = self.model(self.x, self.lens_i32, self.tgt_i32, self.tlen_i32, seed=self.seed0,
-                             specaug_params=self.sa_params)
+        loss, logits = self.model(self.x, self.lens_i32, self.tgt_i32, self.tlen_i32, seed=self.seed0,
+                                  specaug_params=self.sa_params)
+        if self.keep_logits:
+            self.static_logits = logits
         loss.backward(self.one)
         return loss
 
@@ -604,6 +615,7 @@ class Harness:
         for p in probes:
             p.active = False
         grads_timed = [p.grad for p in self.params]
+        logits_timed = self.static_logits
         if probes and not self.probe_inline:
             # a second capture of the same step carries the probe's slot kernels (68 one-lane launches per
             # step); it is replayed after the timed region, so the probes never sit inside `value`'s clock
@@ -619,6 +631,7 @@ class Harness:
                 p.active = False
             for p, g in zip(self.params, grads_timed):
                 p.grad = g           # the timed replays' optimizer steps read the timed graph's grads
+            self.static_logits = logits_timed
         self.step()                  # one replay outside the timed region
         torch.cuda.synchronize()
 
@@ -665,6 +678,46 @@ class Harness:
         for p in self.params:
             ok &= torch.isfinite(p.detach()).all()
         return bool(ok.item())
+
+
+DUMP_LOGITS_ELEMS = 12_500_000     # --dump-outputs: 50 MB of fp32 logits, 6 MB each of gradient / weight samples
+DUMP_SAMPLE_ELEMS = 1_500_000
+
+
+def _seeded_sample(flat, n, seed):
+    """`flat` whole when it has at most n elements, else its elements at n fixed positions (seeded draw, sorted):
+    the same positions in every run of the same shape."""
+    if flat.numel() <= n:
+        return flat
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    idx = torch.randint(0, flat.numel(), (n,), generator=g).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write every (name, tensor) as out_dir/<name>.npy (float32; integer outputs as float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.to(torch.float32) if t.is_floating_point() else t.to(torch.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
+def training_outputs(h):
+    """What the last timed step handed back: the loss, the CTC head's logits (B, T2, V), and -- as fixed seeded samples
+    of the flattened concatenation over the parameters, beside every parameter's full gradient norm -- the gradients it
+    left in .grad and the weights after its optimizer step."""
+    grads = [(p.grad if p.grad is not None else torch.zeros_like(p)).detach().float().reshape(-1) for p in h.params]
+    out = {"loss": h.static_loss.reshape(1),
+           "grad_norms": torch.stack([g.double().norm() for g in grads]).float(),
+           "grads_sample": _seeded_sample(torch.cat(grads), DUMP_SAMPLE_ELEMS, 1),
+           "params_sample": _seeded_sample(torch.cat([p.detach().float().reshape(-1) for p in h.params]),
+                                           DUMP_SAMPLE_ELEMS, 2)}
+    if h.static_logits is not None:
+        out["logits"] = _seeded_sample(h.static_logits.reshape(-1), DUMP_LOGITS_ELEMS, 3).reshape(
+            h.static_logits.shape if h.static_logits.numel() <= DUMP_LOGITS_ELEMS else (-1,))
+    return out
 
 
 def free_port():
@@ -721,7 +774,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="L15", choices=sorted(CONFIGS))
     ap.add_argument("--dropout", type=float, default=0.1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check the rest: the roofline entries (live kernel "
+                         "probes on replays of a second captured step), the CTC head alone, the final weights' "
+                         "finiteness and the CPU baselines (a plain run stops at the headline figure)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32): loss, "
+                         "logits, per-parameter gradient norms, fixed seeded samples of the gradients and of the "
+                         "updated weights (--nst: ids, labels, label_counts); rank 0 only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no-optimizer", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=None,
                     help="CPU baseline threads (default: the host's physical cores, SURVEY.md §8d; a 16-thread "
@@ -749,7 +810,8 @@ def main():
     ap.add_argument("--dp-chunk-layers", type=int, default=4,
                     help="layers per gradient bucket chunk (overlap mode: one graph cut + grouped-wgrad flush each)")
     ap.add_argument("--probe-inline", action="store_true",
-                    help="put the roofline probe kernels inside the timed graph (default: a separate probed graph)")
+                    help="--full: put the roofline probe kernels inside the timed graph (default: a separate probed "
+                         "graph)")
     ap.add_argument("--poison", action="store_true",
                     help="debug: NaN-fill every torch.empty (deterministic algorithms + fill_uninitialized_memory)")
     args = ap.parse_args()
@@ -797,8 +859,10 @@ def main():
     h = Harness(cfg, dev, rank, world, dropout=args.dropout, fp8=args.fp8, specaug=args.specaug,
                 dp_overlap=args.dp_overlap or (world > 1 and not args.no_dp_overlap), eager=args.eager,
                 chunk_layers=args.dp_chunk_layers,
-                no_optimizer=args.no_optimizer, probe_inline=args.probe_inline, grad_bf16=args.grad_bf16)
+                no_optimizer=args.no_optimizer, probe_inline=args.probe_inline, grad_bf16=args.grad_bf16,
+                keep_logits=bool(args.dump_outputs))
     model, T2, T_in = h.model, h.T2, h.T_in
+    # the kernel probes below time launches only in a --full run: a plain run installs no hook and captures no second graph
 
     # dominant kernel: the FFN up-projection GEMM (M=B*T2, N=ffn, K=d, bf16, SiLU epilogue)
     M_ffn = B * T2
@@ -815,10 +879,12 @@ def main():
     # out-projection, pointwise convs) and the folded front-end GEMM (batch x T2 rows)
     dprobe = KernelProbe(lambda kind, shape, dsc: kind == "gemm" and shape[1] == d and shape[0] * dsc.batch == M_ffn
                          and dsc.dtype_ab == _lib.BF16 and dsc.split_k <= 1 and dsc.a_kmajor and dsc.b_kmajor, dev)
-    ops.PROBE = lambda kind, shape, dsc, launch: probe(kind, shape, dsc, lambda: wprobe(
-        kind, shape, dsc, lambda: dprobe(kind, shape, dsc, lambda: fprobe(kind, shape, dsc, launch))))
-    h.setup(args.warmup, probes=(probe, wprobe, dprobe, fprobe))
-    for pr in (probe, wprobe, dprobe, fprobe):
+    probes = (probe, wprobe, dprobe, fprobe) if args.full else ()
+    if args.full:
+        ops.PROBE = lambda kind, shape, dsc, launch: probe(kind, shape, dsc, lambda: wprobe(
+            kind, shape, dsc, lambda: dprobe(kind, shape, dsc, lambda: fprobe(kind, shape, dsc, launch))))
+    h.setup(args.warmup, probes=probes)
+    for pr in probes:
         pr.reset()
     bad_before = h.nonfinite_steps()
 
@@ -826,7 +892,8 @@ def main():
         torch.distributed.barrier()
     torch.cuda.synchronize()
     if h.graph is None:
-        probe.active = wprobe.active = dprobe.active = fprobe.active = True
+        for pr in probes:
+            pr.active = True
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = h.step()
@@ -834,7 +901,8 @@ def main():
     if world > 1:
         torch.distributed.barrier()
     t1 = time.perf_counter()
-    probe.active = wprobe.active = dprobe.active = fprobe.active = False
+    for pr in probes:
+        pr.active = False
     elapsed = t1 - t0
     if world > 1:
         tt = torch.tensor([elapsed], device=dev)
@@ -846,14 +914,79 @@ def main():
               file=sys.stderr)
     frames_total = B * T_in * world * args.steps
     value = frames_total / elapsed
-    # numerics of the timed steps: non-finite losses over every step run (warm-up included) and the final weights
+    # numerics of the timed steps: non-finite losses over every step run (warm-up included; the device counter the
+    # steps themselves kept) and, with --full, the final weights
     loss_val = float(loss.item())
     nonfinite = h.nonfinite_steps()
-    params_ok = h.params_finite()
     if world > 1:
-        tt = torch.tensor([nonfinite, 0 if params_ok else 1], device=dev, dtype=torch.int64)
+        tt = torch.tensor([nonfinite], device=dev, dtype=torch.int64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.SUM)
-        nonfinite, params_ok = int(tt[0].item()), int(tt[1].item()) == 0
+        nonfinite = int(tt[0].item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, training_outputs(h))
+    params_ok = None
+    if args.full:
+        params_ok = h.params_finite()
+        if world > 1:
+            tt = torch.tensor([0 if params_ok else 1], device=dev, dtype=torch.int64)
+            torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.SUM)
+            params_ok = int(tt[0].item()) == 0
+    valid = nonfinite == 0 and params_ok is not False
+
+    _, fpf = algorithmic_flops_per_frame(L, d, H, ffn, K, T_in, T2, model.F2, rel=pos_enc == "rel", B=B)
+    fg = ops.ffold_geometry(B, 80, T_in, 512, 128, d, 7, 2, 3, 2, torch.bfloat16, True)
+    xpf = executed_flops_per_frame(L, d, H, ffn, K, T_in, T2, rel=pos_enc == "rel", B=B, Kp=fg.Kp, T2p=fg.T2p)
+    step_tflops = xpf * B * T_in / (ms_step * 1e-3) / 1e12
+    ref_tflops = fpf * B * T_in / (ms_step * 1e-3) / 1e12
+    # the result line of a plain run: the headline figure, the step's configuration and FLOP counts (arithmetic on
+    # ms_per_step) and the numerics the timed steps recorded themselves; --full adds its entries below
+    result = {
+        "metric": METRIC, "value": round(value, 1), "unit": "mel-frames/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "fp8-e4m3 fwd GEMMs + bf16" if args.fp8 else "bf16",
+        "data": "synthetic (uniform min-max-normalised 80-bin mels, random init)",
+        "config": {"workload": f"{name} encoder fwd+bwd + CTC head, {B} x {secs} s utterances per GPU",
+                   "model": name, "layers": L, "d_model": d, "heads": H, "ffn": ffn, "conv_kernel": K,
+                   "pos_enc": pos_enc, "specaug": bool(args.specaug),
+                   "global_batch": B * world, "seq_len": T_in, "enc_frames": T2, "frontend": "frame",
+                   "dropout": args.dropout, "optimizer": None if args.no_optimizer else "adafactor",
+                   "parallelism": f"dp{world}",
+                   "launch": "eager" if h.eager else (f"hip-graph chain ({len(h.seg)} segments, bucket all-reduce "
+                                                      "between replays)" if h.seg is not None
+                                                      else "hip-graph (fwd+bwd)"),
+                   "grad_reduce_dtype": "bf16" if h.reducer.grad_dtype == torch.bfloat16 else "fp32",
+                   **({"dp_chunk_layers": args.dp_chunk_layers} if h.seg is not None else {})},
+        "per_gpu_value": round(value / world, 1),
+        "dist_backend": torch.distributed.get_backend() if torch.distributed.is_initialized() else None,
+        "world_size_reported": torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1,
+        # FLOPs the step executes (encoder + the folded front-end GEMMs; CTC head excluded), and the reference
+        # composition's count (conv1 + conv2 + projection as the reference computes them) beside it
+        "step_executed_tflops": round(step_tflops, 1),
+        "step_mfma_frac": round(step_tflops / PEAK_BF16_TFLOPS, 4),
+        "step_flops_basis": "executed: encoder (SURVEY.md 8d per-layer MACs) + folded front-end GEMMs; CTC head "
+                            "excluded (rounds 1-4 records named this key step_algorithmic_tflops; since round 4 it "
+                            "is the executed count, the reference composition's is step_ref_composition_tflops)",
+        "step_ref_composition_tflops": round(ref_tflops, 1),
+        "loss": loss_val,
+        "steps_checked": h.steps_run, "nonfinite_steps": nonfinite, "nonfinite_before_timing": bad_before,
+        "ctc_recursion_aborts": int(h.ctc_aborts.item()),
+        "valid": valid, "full": bool(args.full),
+    }
+    if args.poison:
+        result["poison"] = True
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        if not valid:
+            print(f"bench: INVALID step numerics: {nonfinite} of {h.steps_run} steps had a non-finite loss, "
+                  f"parameters finite: {params_ok}", file=sys.stderr)
+            sys.exit(3)
+
+    if not args.full:
+        return finish()
 
     h.probe_replays(args.steps)
     ops.PROBE = None
@@ -875,11 +1008,6 @@ def main():
     wg_shapes = [(d, ffn), (ffn, d)] * 2 + [(3 * d, d), (d, d), (2 * d, d), (d, d)]   # (N, K) per layer
     wg_flops = 2.0 * M_ffn * L * sum(n * k for n, k in wg_shapes)
     wg_bytes = L * sum(2.0 * M_ffn * (n + k) + 4.0 * n * k + 4.0 * n for n, k in wg_shapes)
-    _, fpf = algorithmic_flops_per_frame(L, d, H, ffn, K, T_in, T2, model.F2, rel=pos_enc == "rel", B=B)
-    fg = ops.ffold_geometry(B, 80, T_in, 512, 128, d, 7, 2, 3, 2, torch.bfloat16, True)
-    xpf = executed_flops_per_frame(L, d, H, ffn, K, T_in, T2, rel=pos_enc == "rel", B=B, Kp=fg.Kp, T2p=fg.T2p)
-    step_tflops = xpf * B * T_in / (ms_step * 1e-3) / 1e12
-    ref_tflops = fpf * B * T_in / (ms_step * 1e-3) / 1e12
     ctc_ms = time_ctc_head(h) if rank == 0 else float("nan")
 
     cfg_key = args.config + ("+fp8" if args.fp8 else "") + ("+specaug" if args.specaug else "") + (
@@ -943,42 +1071,12 @@ def main():
                 break
         return e
 
-    valid = nonfinite == 0 and params_ok
-    result = {
-        "metric": METRIC, "value": round(value, 1), "unit": "mel-frames/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "fp8-e4m3 fwd GEMMs + bf16" if args.fp8 else "bf16",
-        "data": "synthetic (uniform min-max-normalised 80-bin mels, random init)",
-        "config": {"workload": f"{name} encoder fwd+bwd + CTC head, {B} x {secs} s utterances per GPU",
-                   "model": name, "layers": L, "d_model": d, "heads": H, "ffn": ffn, "conv_kernel": K,
-                   "pos_enc": pos_enc, "specaug": bool(args.specaug),
-                   "global_batch": B * world, "seq_len": T_in, "enc_frames": T2, "frontend": "frame",
-                   "dropout": args.dropout, "optimizer": None if args.no_optimizer else "adafactor",
-                   "parallelism": f"dp{world}",
-                   "launch": "eager" if h.eager else (f"hip-graph chain ({len(h.seg)} segments, bucket all-reduce "
-                                                      "between replays)" if h.seg is not None
-                                                      else "hip-graph (fwd+bwd)"),
-                   "grad_reduce_dtype": "bf16" if h.reducer.grad_dtype == torch.bfloat16 else "fp32",
-                   **({"dp_chunk_layers": args.dp_chunk_layers} if h.seg is not None else {})},
-        "per_gpu_value": round(value / world, 1),
-        "dist_backend": torch.distributed.get_backend() if torch.distributed.is_initialized() else None,
-        "world_size_reported": torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1,
-        # FLOPs the step executes (encoder + the folded front-end GEMMs; CTC head excluded), and the reference
-        # composition's count (conv1 + conv2 + projection as the reference computes them) beside it
-        "step_executed_tflops": round(step_tflops, 1),
-        "step_mfma_frac": round(step_tflops / PEAK_BF16_TFLOPS, 4),
-        "step_flops_basis": "executed: encoder (SURVEY.md 8d per-layer MACs) + folded front-end GEMMs; CTC head "
-                            "excluded (rounds 1-4 records named this key step_algorithmic_tflops; since round 4 it "
-                            "is the executed count, the reference composition's is step_ref_composition_tflops)",
-        "step_ref_composition_tflops": round(ref_tflops, 1),
+    result.update({
         "ctc_head": {"ms": round(ctc_ms, 4), "share_of_step": round(ctc_ms / ms_step, 4),
                      "flops": 3 * 2.0 * B * T2 * d * h.V,
                      "timing": "fused Linear + log_softmax + CTC fwd+bwd alone at the step's shape, one HIP graph "
                                "replayed 20x after the timed region (HIP events); it runs inside the timed step"},
-        "loss": loss_val,
-        "steps_checked": h.steps_run, "nonfinite_steps": nonfinite, "nonfinite_before_timing": bad_before,
-        "ctc_recursion_aborts": int(h.ctc_aborts.item()),
-        "params_finite": params_ok, "valid": valid,
+        "params_finite": params_ok,
         # the dominant kernel family: d-wide-output GEMMs (mean FLOP / mean launch; bytes per launch from its
         # descriptor (gemm_desc_bytes): A + B read, C written in its dtype -- bf16 data gradients, fp32
         # residual-stream forwards written + residual read -- averaged likewise)
@@ -992,7 +1090,7 @@ def main():
         "roofline_wgrad": roofline_entry(f"grouped weight gradients (cfm_wgrad_group): {L} layers x 8 GEMMs, "
                                          f"M={M_ffn} tokens", wg_flops, wg_bytes, wprobe, "wgrad_group_pmc.json",
                                          "wgrad"),
-    }
+    })
     if probe.mean_ms()[1] == 0:      # --fp8: the FFN up-projection runs on fp8 (roofline_fp8 below)
         del result["roofline_ffn_up"]
     if fprobe.mean_ms()[1] > 0:
@@ -1002,8 +1100,6 @@ def main():
             f"MX e4m3 forward GEMMs (v_mfma_scale_f32_32x32x64_f8f6f4, gemm_pipe F8): FFN up / down, QKV, out-projection, "
             f"{fprobe.mean_ms()[1] // max(1, args.steps)} launches per step", fprobe.mean_flops(), fprobe.mean_bytes(),
             fprobe, "gemm_fp8_pmc.json", "fp8", peak_tflops=PEAK_FP8_TFLOPS)
-    if args.poison:
-        result["poison"] = True
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         # thread sweep up to the host's physical cores (64 per socket on the pool's EPYC 9575F); the job's CPU
         # quota (cgroup cpu.max) may be far below that, so the fastest count is the baseline and the sweep is
@@ -1017,14 +1113,7 @@ def main():
                                       cgroup_cpu_quota=quota,
                                       thread_sweep={str(t): v["value"] for t, v in sweep.items()})
         result["cpu_baseline_configs0"] = cpu_baseline_s10(best)
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if world > 1:
-        torch.distributed.destroy_process_group()
-    if not valid:
-        print(f"bench: INVALID step numerics: {nonfinite} of {h.steps_run} steps had a non-finite loss, "
-              f"parameters finite: {params_ok}", file=sys.stderr)
-        sys.exit(3)
+    finish()
 
 
 if __name__ == "__main__":

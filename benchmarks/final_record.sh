@@ -20,7 +20,7 @@ step() {   # name limit cmd
 trace() {   # key steps warmup bench-args...
   local key=$1 st=$2 wu=$3; shift 3
   step "trace_$key" 600 "cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv \
-    -d $OUT/trace_$key -o run -- python3 $R/bench.py --steps $st --warmup $wu --no-cpu-baseline $* \
+    -d $OUT/trace_$key -o run -- python3 $R/bench.py --full --steps $st --warmup $wu --no-cpu-baseline $* \
     > $OUT/trace_bench_$key.json && python3 $R/profiles/summarize_trace.py \
     \$(find $OUT/trace_$key -name '*kernel_trace.csv' | head -1) $OUT/trace_$key.json --config '$key' --warmup $wu \
     --steps $st --lib $LIB > $OUT/trace_summary_$key.txt && python3 $R/profiles/summarize.py \
