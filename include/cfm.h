@@ -274,15 +274,71 @@ int cfm_wgrad_group_fill_split(void* host_table, int i, const void* dy, const vo
                                int N, int K, int split, float* ws, long red0);
 int cfm_wgrad_group_sched(const void* dev_table, int ntasks, const unsigned* dev_sched, long grid, long red_blocks,
                           unsigned long long* probe, void* stream);
-/* kernel-selection switch for A/B measurements: bit 0 = 256-row register-staged tiles allowed,
-   bit 1 = LDS-DMA pipelined kernel allowed, bit 3 = timing experiment (pipelined kernels skip their
-   stores), bits 4-6 = pipelined variant (0 auto, 1 256x128/BK64, 2 256x128/BK32 two per CU,
-   5 192x128, 7 192x128/BK32 two per CU), bit 10 = generic dropout hash path, bit 12 = no 192-row rule for
-   1024/1536-wide outputs, bit 13 = timing experiment (main loop skipped: epilogue only), bit 14 = generic
-   epilogue rows instead of the compile-time epilogue kinds, bit 19 = shared-DMA pipeline instead of the
-   warp-specialised kernel for d-wide outputs, bit 21 = 192-row pipeline instead of the warp-specialised kernel
-   for 1024/1536-wide outputs; default 3. */
+/* cfm_gemm_set_mode: the kernel-selection word, for A/B measurements and the tests that compare variants bit for
+   bit.  These enumerators are the one description of its bits (nn_conformer_for_speech_recognition_amd/_lib.py
+   mirrors them as GEMM_MODE_*); bits without a name are read by nothing. */
+enum cfm_gemm_mode {
+  CFM_GEMM_MODE_STAGED256 = 1 << 0,       /* keeps the 256-row register-staged bf16 tiles allowed */
+  CFM_GEMM_MODE_PIPE = 1 << 1,            /* keeps the LDS-DMA kernels (pipeline, warp-specialised, conv2) allowed */
+  CFM_GEMM_MODE_DEFAULT = 3,              /* STAGED256 | PIPE */
+  CFM_GEMM_MODE_SKIP_STORES = 1 << 3,     /* timing: LDS-DMA kernels skip the epilogue's stores (outputs invalid) */
+  CFM_GEMM_MODE_SEL_SHIFT = 4,            /* bits 4-6: force one bf16 pipeline variant, CFM_GEMM_SEL_* << SEL_SHIFT */
+  CFM_GEMM_MODE_SEL_MASK = 7 << 4,
+  CFM_GEMM_MODE_GENERIC_DROPOUT = 1 << 10, /* keeps the generic dropout hash path of the epilogue */
+  CFM_GEMM_MODE_NO_192S8_RULE = 1 << 12,  /* skips the 192-row rule for 513..1536-wide outputs of short reductions */
+  CFM_GEMM_MODE_SKIP_MAINLOOP = 1 << 13,  /* timing: LDS-DMA kernels skip the main loop (epilogue only) */
+  CFM_GEMM_MODE_GENERIC_EPILOGUE = 1 << 14, /* keeps the generic epilogue rows instead of the compile-time kinds */
+  CFM_GEMM_MODE_KEEP_SHARED_DMA = 1 << 19, /* keeps the 4-deep 192-row pipeline where the warp-specialised kernel runs */
+  CFM_GEMM_MODE_KEEP_PIPE192 = 1 << 21,   /* keeps the two-per-CU 192-row pipeline for 513..1536-wide outputs */
+  CFM_GEMM_MODE_KEEP_128WIDE = 1 << 22,   /* keeps 128-wide tiles for 129..160-column outputs (skips the 64 x 160 tile) */
+  CFM_GEMM_MODE_KEEP_WS192 = 1 << 23      /* keeps the 192-row warp-specialised tiles where 96-row ones would run */
+};
+/* values of the selector field (only the variants a layout has are forced; anything else means auto) */
+enum cfm_gemm_sel {
+  CFM_GEMM_SEL_AUTO = 0,
+  CFM_GEMM_SEL_PIPE256 = 1,               /* 256 x 128, BK 64, one workgroup per CU */
+  CFM_GEMM_SEL_PIPE256S = 2,              /* 256 x 128, BK 32, two per CU */
+  CFM_GEMM_SEL_192 = 5,                   /* 192 x 128: warp-specialised (K-major x K-major) or the 4-deep pipeline */
+  CFM_GEMM_SEL_PIPE192S8 = 7              /* 192 x 128, BK 32, two per CU */
+};
 int cfm_gemm_set_mode(int mode);
+
+/* The kernel a cfm_gemm call runs (csrc/gemm_variants.h documents each variant's geometry). */
+enum cfm_gemm_variant {
+  CFM_GEMM_V_NONE = 0,                    /* M == 0 or N == 0: nothing is launched */
+  CFM_GEMM_V_STAGED_BF16_256,             /* register-staged bf16, 256 x 128 tiles */
+  CFM_GEMM_V_STAGED_BF16_128,             /* register-staged bf16, 128 x 128 tiles */
+  CFM_GEMM_V_STAGED_F32_128,              /* register-staged fp32, 128 x 128 tiles */
+  CFM_GEMM_V_STAGED_F32_64,               /* register-staged fp32, 64 x 64 tiles */
+  CFM_GEMM_V_PIPE64X160,                  /* LDS-DMA pipeline, 64 x 160 tiles */
+  CFM_GEMM_V_WS192,                       /* warp-specialised, 192 x 128 tiles */
+  CFM_GEMM_V_WS96,                        /* warp-specialised, 96 x 128 tiles */
+  CFM_GEMM_V_PIPE192,                     /* pipeline, 192 x 128, BK 64, 4-deep ring */
+  CFM_GEMM_V_PIPE192S8,                   /* pipeline, 192 x 128, BK 32, two per CU */
+  CFM_GEMM_V_PIPE256,                     /* pipeline, 256 x 128, BK 64 */
+  CFM_GEMM_V_PIPE256S,                    /* pipeline, 256 x 128, BK 32, two per CU */
+  CFM_GEMM_V_FP8_192,                     /* per-tensor fp8, 192 x 128 */
+  CFM_GEMM_V_FP8_256S,                    /* per-tensor fp8, 256 x 128, two per CU */
+  CFM_GEMM_V_MX192,                       /* MX fp8, 192 x 128 */
+  CFM_GEMM_V_MX256S                       /* MX fp8, 256 x 128, two per CU */
+};
+/* The staged epilogue a launch carries: GENERIC is the run-time epilogue rows, every other kind a body fixed at
+   compile time (csrc/gemm_epilogue.h). */
+enum cfm_gemm_epilogue {
+  CFM_GEMM_EPI_GENERIC = 0, CFM_GEMM_EPI_BF16 = 1, CFM_GEMM_EPI_BF16_BIAS = 2, CFM_GEMM_EPI_BF16_SILU = 3,
+  CFM_GEMM_EPI_BF16_ACTG = 4, CFM_GEMM_EPI_BF16_RD = 5, CFM_GEMM_EPI_F32 = 6, CFM_GEMM_EPI_F32_RES = 7,
+  CFM_GEMM_EPI_BF16_SILU_MX = 8, CFM_GEMM_EPI_BF16_RES = 9, CFM_GEMM_EPI_F32R_BF16 = 10, CFM_GEMM_EPI_BF16_DELTA = 11
+};
+typedef struct {
+  int variant;                            /* cfm_gemm_variant */
+  int epilogue;                           /* cfm_gemm_epilogue */
+  unsigned grid_x, grid_y, grid_z;
+  unsigned block;
+} cfm_gemm_choice;
+/* What cfm_gemm(d) would launch under `mode` (< 0: the current cfm_gemm_set_mode value) on a device of `cus`
+   compute units: the same validation and selection as cfm_gemm, the same error codes, and no launch -- it calls
+   no GPU API and reads only the values and alignment of the descriptor's pointers. */
+int cfm_gemm_plan(const cfm_gemm_desc* d, int mode, int cus, cfm_gemm_choice* out);
 
 /* out[n] (+)= sum_m x[m*ld + n]  — bias gradients (sum over tokens).  ws: >= 4*N*256 bytes. */
 /* out[n] (+)= sum_p part[p * ldp + n] for n < N: the deterministic second level of every partial-row
@@ -407,12 +463,18 @@ int cfm_glu_dwconv_bwd_bn(const void* dz, int dtype_dz, const float* y, const fl
  * qkv: (B*T, 3*H*dk) rows [q | k | v]; o: (B*T, H*dk); lse: (B*H*T) fp32 log-sum-exp per query
  * (saved for backward); lengths: (B) int32 valid keys.  pos (rel only): (2T-1, H*dk) projected
  * table; pos_u / pos_v: (H*dk) fp32.  dtype: CFM_BF16 (MFMA) or CFM_F32. */
-/* A/B switch (measurement only): bit 0 forces the tiled attention kernels instead of the
-   whole-head ones (T <= 384: one workgroup per (b, h) with K/V staged once in LDS); bits 1-2 timing
-   experiments of the whole-head forward (value 2: staging only, 4: no output stores -- outputs invalid);
-   bit 4 runs bf16 relative-position attention on the SIMT kernels (parity cross-check); bit 6 keeps the
-   rel-pos kernels' zero-filling (non-clamped) tile loads; bit 7 runs the round-4 rel-pos dpos kernel (one
-   workgroup per (utterance, head, 64 relative rows); the round-5 kernel is checked against it). */
+/* cfm_attn_set_mode: A/B switches (measurement and cross-check tests only); default 0.  These enumerators are
+   the one description of the bits (mirrored as ATTN_MODE_* in _lib.py). */
+enum cfm_attn_mode {
+  CFM_ATTN_MODE_TILED = 1 << 0,           /* skips the whole-head kernels (T <= 384): the tiled ones run */
+  CFM_ATTN_MODE_STAGING_ONLY = 1 << 1,    /* timing: the whole-head forward stops after staging (outputs invalid) */
+  CFM_ATTN_MODE_SKIP_STORES = 1 << 2,     /* timing: the whole-head forward skips its output stores */
+  CFM_ATTN_MODE_REL_SIMT = 1 << 4,        /* keeps bf16 relative-position attention on the SIMT kernels */
+  CFM_ATTN_MODE_REL_ZERO_FILL = 1 << 6,   /* keeps the rel-pos kernels' zero-filling tile loads; one forward row block */
+  CFM_ATTN_MODE_REL_DPOS_R4 = 1 << 7,     /* keeps the round-4 rel-pos dpos kernel */
+  CFM_ATTN_MODE_REL_DQ_RECOMPUTE = 1 << 9, /* keeps the recomputing rel-pos dQ2 kernel (default: dQ from the stored dS) */
+  CFM_ATTN_MODE_DQ_RECOMPUTE = 1 << 10    /* keeps the recomputing whole-head dQ kernel (default: the stored dS) */
+};
 int cfm_attn_set_mode(int mode);
 int cfm_attn_fwd(const void* qkv, void* o, float* lse, const int32_t* lengths, const void* pos,
                  const float* pos_u, const float* pos_v, int B, int T, int H, int dk, int dtype,

@@ -49,6 +49,48 @@ class GemmDesc(ctypes.Structure):
     ]
 
 
+class GemmChoice(ctypes.Structure):
+    """cfm_gemm_choice (include/cfm.h): what cfm_gemm_plan says a cfm_gemm call would launch."""
+    _fields_ = [("variant", c_int), ("epilogue", c_int), ("grid_x", ctypes.c_uint), ("grid_y", ctypes.c_uint),
+                ("grid_z", ctypes.c_uint), ("block", ctypes.c_uint)]
+
+
+# Mirrors of the enums of include/cfm.h (tests/test_gemm_plan_cpu.py holds them equal to the header).
+# cfm_gemm_mode (cfm_gemm_set_mode) and cfm_gemm_sel (its selector field, GEMM_SEL_* << GEMM_MODE_SEL_SHIFT)
+GEMM_MODE_STAGED256 = 1 << 0
+GEMM_MODE_PIPE = 1 << 1
+GEMM_MODE_DEFAULT = 3
+GEMM_MODE_SKIP_STORES = 1 << 3
+GEMM_MODE_SEL_SHIFT = 4
+GEMM_MODE_SEL_MASK = 7 << 4
+GEMM_MODE_GENERIC_DROPOUT = 1 << 10
+GEMM_MODE_NO_192S8_RULE = 1 << 12
+GEMM_MODE_SKIP_MAINLOOP = 1 << 13
+GEMM_MODE_GENERIC_EPILOGUE = 1 << 14
+GEMM_MODE_KEEP_SHARED_DMA = 1 << 19
+GEMM_MODE_KEEP_PIPE192 = 1 << 21
+GEMM_MODE_KEEP_128WIDE = 1 << 22
+GEMM_MODE_KEEP_WS192 = 1 << 23
+GEMM_SEL_AUTO, GEMM_SEL_PIPE256, GEMM_SEL_PIPE256S, GEMM_SEL_192, GEMM_SEL_PIPE192S8 = 0, 1, 2, 5, 7
+# cfm_gemm_variant
+(GEMM_V_NONE, GEMM_V_STAGED_BF16_256, GEMM_V_STAGED_BF16_128, GEMM_V_STAGED_F32_128, GEMM_V_STAGED_F32_64,
+ GEMM_V_PIPE64X160, GEMM_V_WS192, GEMM_V_WS96, GEMM_V_PIPE192, GEMM_V_PIPE192S8, GEMM_V_PIPE256, GEMM_V_PIPE256S,
+ GEMM_V_FP8_192, GEMM_V_FP8_256S, GEMM_V_MX192, GEMM_V_MX256S) = range(16)
+# cfm_gemm_epilogue
+(GEMM_EPI_GENERIC, GEMM_EPI_BF16, GEMM_EPI_BF16_BIAS, GEMM_EPI_BF16_SILU, GEMM_EPI_BF16_ACTG, GEMM_EPI_BF16_RD,
+ GEMM_EPI_F32, GEMM_EPI_F32_RES, GEMM_EPI_BF16_SILU_MX, GEMM_EPI_BF16_RES, GEMM_EPI_F32R_BF16,
+ GEMM_EPI_BF16_DELTA) = range(12)
+# cfm_attn_mode (cfm_attn_set_mode)
+ATTN_MODE_TILED = 1 << 0
+ATTN_MODE_STAGING_ONLY = 1 << 1
+ATTN_MODE_SKIP_STORES = 1 << 2
+ATTN_MODE_REL_SIMT = 1 << 4
+ATTN_MODE_REL_ZERO_FILL = 1 << 6
+ATTN_MODE_REL_DPOS_R4 = 1 << 7
+ATTN_MODE_REL_DQ_RECOMPUTE = 1 << 9
+ATTN_MODE_DQ_RECOMPUTE = 1 << 10
+
+
 class FfoldGeo(ctypes.Structure):
     """cfm_ffold_geo (include/cfm.h): the folded front-end geometry; cfm_ffold_geometry fills the derived fields."""
     _fields_ = [(n, c_int) for n in ("B", "F", "T", "C1", "C2", "D", "k1", "s1", "k2", "s2", "dtype", "hilo",
@@ -72,6 +114,7 @@ _SIGS = {
                                c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "cfm_gemm": (c_int, [ctypes.POINTER(GemmDesc), c_void_p]),
     "cfm_gemm_set_mode": (c_int, [c_int]),
+    "cfm_gemm_plan": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "cfm_quant_fp8": (c_int, [c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cfm_quant_fp8_ws_bytes": (c_size_t, []),
     "cfm_quant_fp8_batch_blocks": (c_long, [c_long]),

@@ -569,7 +569,7 @@ __global__ __launch_bounds__(64 * HEAD_TMAX / 32) void attn_bwd_dkdv_wave_kernel
 }
 
 // ------------------------------------------------------------------------------------ dQ from the stored dS^T
-// (round 6 default on the whole-head path when the caller passes the full workspace; cfm_attn_set_mode bit 10 keeps
+// (round 6 default on the whole-head path when the caller passes the full workspace; CFM_ATTN_MODE_DQ_RECOMPUTE keeps
 // attn_bwd_dq_head_kernel).  dq_i = scale * sum_j dS_ij k_j over the dS^T that attn_bwd_dkdv_wave_kernel stored:
 // 8 MFMAs per 64-key tile and wave, no score / softmax / dropout-hash / dO x V recompute.  Whole-head layout like the
 // other head kernels: grid (B*H*qs), one wave per 32-query block; the head's K is staged once (192-B rows: the
@@ -872,14 +872,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(AttnM p, const bf16*
 }
 
 // bf16 runs on MFMA (pos != nullptr: attention_rel.hip); fp32 (the parity mode) on the SIMT kernels.
-// cfm_attn_set_mode bit 4 sends bf16 rel-pos back to SIMT (A/B, parity cross-check).
+// CFM_ATTN_MODE_REL_SIMT sends bf16 rel-pos back to SIMT (A/B, parity cross-check).
 int g_attn_mode = 0;
 bool use_mfma(int dtype, const void* pos, int dk) {
-  return dtype == CFM_BF16 && dk <= DKP && (pos == nullptr || (g_attn_mode & 16) == 0);
+  return dtype == CFM_BF16 && dk <= DKP && (pos == nullptr || (g_attn_mode & CFM_ATTN_MODE_REL_SIMT) == 0);
 }
 
-// whole-head kernels: T <= HEAD_TMAX; cfm_attn_set_mode bit 0 forces the tiled kernels (A/B, parity)
-bool use_head(int T) { return T <= HEAD_TMAX && (g_attn_mode & 1) == 0; }
+// whole-head kernels: T <= HEAD_TMAX; CFM_ATTN_MODE_TILED forces the tiled kernels (A/B, parity)
+bool use_head(int T) { return T <= HEAD_TMAX && (g_attn_mode & CFM_ATTN_MODE_TILED) == 0; }
 size_t head_lds_bytes(int T, int waves) {
   const size_t rows = (size_t)cdiv(T, TILE) * TILE;
   const size_t img = 2 * rows * KS * sizeof(bf16);
@@ -887,22 +887,12 @@ size_t head_lds_bytes(int T, int waves) {
   return img > stage ? img : stage;
 }
 
-int attn_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-  }
-  return n;
-}
 
 // workgroups per (b, h) of the whole-head kernels: enough to give every CU one (B*H*qs <= CUs), at most 4 and at most
-// one 32-row block each (cfm_attn_set_mode bit 6: always one, A/B)
+// one 32-row block each (CFM_ATTN_MODE_REL_ZERO_FILL: always one, A/B)
 int head_split(int B, int H, int T) {
-  if (g_attn_mode & 64) return 1;
-  const int nb = cdiv(T, 32), bh = B * H, cus = attn_num_cus();
+  if (g_attn_mode & CFM_ATTN_MODE_REL_ZERO_FILL) return 1;
+  const int nb = cdiv(T, 32), bh = B * H, cus = cfm::num_cus();
   int qs = 1;
   while (qs < 4 && qs < nb && (long)bh * (qs + 1) <= cus) ++qs;
   return qs;
@@ -925,7 +915,7 @@ CFM_EXPORT int cfm_attn_fwd(const void* qkv, void* o, float* lse, const int32_t*
   if (pos)
     return cfm::attn_rel_fwd_launch(qkv, o, lse, lengths, pos, pos_u, pos_v, B, T, H, dk, drop_p, seed, s);
   AttnM p{(const bf16*)qkv, B, T, H, dk, 3 * H * dk, H * dk, lengths, 1.f / sqrtf((float)dk), drop_p, seed,
-          ((uintptr_t)qkv % 16 == 0) && (dk % 8 == 0) && ((3 * H * dk) % 8 == 0), g_attn_mode & 6,
+          ((uintptr_t)qkv % 16 == 0) && (dk % 8 == 0) && ((3 * H * dk) % 8 == 0), g_attn_mode & (CFM_ATTN_MODE_STAGING_ONLY | CFM_ATTN_MODE_SKIP_STORES),
           cfm::g_rng_salt};
   p.vec4 = ((uintptr_t)qkv % 8 == 0) && (dk % 4 == 0) && ((3 * H * dk) % 4 == 0);
   if (use_head(T)) {
@@ -941,7 +931,7 @@ CFM_EXPORT int cfm_attn_fwd(const void* qkv, void* o, float* lse, const int32_t*
 }
 
 // the whole-head backward's dS^T buffer (dQ from dS): after D in the full workspace
-static bool dsT_path(int T) { return use_head(T) && !(g_attn_mode & 1024); }
+static bool dsT_path(int T) { return use_head(T) && !(g_attn_mode & CFM_ATTN_MODE_DQ_RECOMPUTE); }
 static size_t d_slot_bytes(int B, int T, int H) { return ((size_t)B * H * T * sizeof(float) + 255) & ~(size_t)255; }
 static size_t dsT_bytes(int B, int T, int H) { const size_t tq = (size_t)cdiv(T, 32) * 32; return (size_t)B * H * tq * tq * 2; }
 
@@ -969,7 +959,7 @@ static int attn_bwd_impl(const void* qkv, const void* o, const void* dout, const
                                      dpos_v, B, T, H, dk, dtype, drop_p, seed, ws, s);
   AttnM p{(const bf16*)qkv, B, T, H, dk, 3 * H * dk, H * dk, lengths, 1.f / sqrtf((float)dk), drop_p, seed,
           ((uintptr_t)qkv % 16 == 0) && ((uintptr_t)dout % 16 == 0) && (dk % 8 == 0) && ((3 * H * dk) % 8 == 0),
-          g_attn_mode & 6, cfm::g_rng_salt};
+          g_attn_mode & (CFM_ATTN_MODE_STAGING_ONLY | CFM_ATTN_MODE_SKIP_STORES), cfm::g_rng_salt};
   p.vec4 = ((uintptr_t)qkv % 8 == 0) && ((uintptr_t)dout % 8 == 0) && (dk % 4 == 0) && ((3 * H * dk) % 4 == 0);
   const long nrow = (long)B * H * T;
   (void)nrow;

@@ -16,7 +16,7 @@
 // Backward (deterministic, no atomics):
 //   dQ kernel  (round 6 default, attn_rel_bwd_dqs_kernel): runs after dK/dV and reads the dS it stored --
 //              dq = scale * (sum_j dS k_j + sum_j dS p_{T-1-i+j}), the band sum as below; no recompute.
-//   dQ2 kernel (queries on the lanes, streams key tiles; cfm_attn_set_mode bit 9): recomputes S (same band), dP, dS;
+//   dQ2 kernel (queries on the lanes, streams key tiles; CFM_ATTN_MODE_REL_DQ_RECOMPUTE): recomputes S (same band), dP, dS;
 //              dq = scale * (sum_j dS k_j  +  sum_j dS p_{T-1-i+j}) -- the second sum is a plain
 //              MFMA over the band once dS^T is scattered into the stage in band coordinates;
 //              per-wave column sums of both terms -> du, dv partials (one reduction launch).
@@ -547,7 +547,7 @@ __global__ __launch_bounds__(256, 2) void attn_rel_bwd_dq2_kernel(AttnM p, RelP 
 }
 
 // ------------------------------------------------------------------------------------ dQ from the stored dS
-// (default since round 6; cfm_attn_set_mode bit 9 keeps the recomputing dQ2 kernel above, A/B).  The dK/dV kernel
+// (default since round 6; CFM_ATTN_MODE_REL_DQ_RECOMPUTE keeps the recomputing dQ2 kernel above, A/B).  The dK/dV kernel
 // already writes dS (bf16, unscaled, query-major) for the dpos pass; dQ is a plain product of it with K and, in band
 // coordinates, with the projected table:  dq_i = scale * (sum_j dS_ij k_j + sum_j dS_ij p_{T-1-i+j}).  No scores,
 // softmax, dropout hash or dO x V recompute: per 64-key tile a wave runs 8 + 12 MFMAs (dQ2: 48) and no exp.
@@ -1295,10 +1295,12 @@ static RelP make_relp(const void* pos, const float* pu, const float* pv, int dk)
   return RelP{(const bf16*)pos, pu, pv, ((uintptr_t)pos % 16 == 0) && (dk % 8 == 0)};
 }
 
-// branch-free prefetch kernels (ld8c): dk = 64 with 16-B aligned rows of qkv / dout / pos.  cfm_attn_set_mode
-// bit 6 keeps the zero-filling loads (A/B)
+// branch-free prefetch kernels (ld8c): dk = 64 with 16-B aligned rows of qkv / dout / pos.
+// CFM_ATTN_MODE_REL_ZERO_FILL keeps the zero-filling loads (A/B)
 int g_rel_mode = 0;
-static bool rel_vec(const AttnM& p, const RelP& rp) { return p.vec && rp.pvec && p.dk == 64 && !(g_rel_mode & 64); }
+static bool rel_vec(const AttnM& p, const RelP& rp) {
+  return p.vec && rp.pvec && p.dk == 64 && !(g_rel_mode & CFM_ATTN_MODE_REL_ZERO_FILL);
+}
 
 static AttnM make_attnm(const void* qkv, const void* dout, const int32_t* len, int B, int T, int H, int dk,
                         float drop_p, uint64_t seed) {
@@ -1330,8 +1332,8 @@ int attn_rel_bwd_launch(const void* qkv, const void* dout, const float* lse, con
   bf16* dsbuf = reinterpret_cast<bf16*>(reinterpret_cast<char*>(part) + part_bytes);
   const int ldS = rel_ldS(p.T);
   const dim3 grid(cdiv(p.T, 128), p.H, p.B);
-  // dK / dV (+ the dS buffer), then dQ: from the stored dS (default) or recomputed (cfm_attn_set_mode bit 9)
-  const bool dq_recompute = (g_rel_mode & 512) != 0;
+  // dK / dV (+ the dS buffer), then dQ: from the stored dS (default) or recomputed (CFM_ATTN_MODE_REL_DQ_RECOMPUTE)
+  const bool dq_recompute = (g_rel_mode & CFM_ATTN_MODE_REL_DQ_RECOMPUTE) != 0;
   if (rel_vec(p, rp)) {
     hipLaunchKernelGGL(attn_rel_bwd_dkdv_kernel<true>, grid, dim3(256), 0, s, p, rp, (const bf16*)dout, lse, ws,
                        (bf16*)dqkv, dsbuf, ldS);
@@ -1353,7 +1355,7 @@ int attn_rel_bwd_launch(const void* qkv, const void* dout, const float* lse, con
   }
   const size_t ds_bytes = ((size_t)p.B * p.H * p.T * ldS * sizeof(bf16) + 255) & ~(size_t)255;
   float* dpos_part = reinterpret_cast<float*>(reinterpret_cast<char*>(dsbuf) + ds_bytes);
-  if (rel_vec(p, rp) && !(g_rel_mode & 128)) {
+  if (rel_vec(p, rp) && !(g_rel_mode & CFM_ATTN_MODE_REL_DPOS_R4)) {
     const int nrt = cdiv(2 * p.T - 1, DP_R);
     hipLaunchKernelGGL(attn_rel_bwd_dpos3_kernel, dim3(8 * cdiv(p.B * p.H, 8) * nrt), dim3(256), 0, s, p, rp,
                        (const bf16*)dsbuf, ldS, dpos_part, nrt);

@@ -19,7 +19,7 @@ struct AttnM {
   float scale;
   float drop_p; uint64_t seed;
   bool vec;    // 16-B vector loads legal
-  int dbg;     // timing experiments (cfm_attn_set_mode bits 1-2)
+  int dbg;     // timing experiments (CFM_ATTN_MODE_STAGING_ONLY / SKIP_STORES)
   const uint64_t* salt;   // bound dropout step counter or nullptr
   bool vec4;   // 8-B vector loads legal (dk % 4 == 0, 8-B aligned rows: Conformer-S's dk 36)
   int qs;      // whole-head kernels: workgroups per (b, h), each a contiguous range of 32-row blocks (<= 1: one)

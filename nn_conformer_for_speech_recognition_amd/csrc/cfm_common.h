@@ -37,6 +37,8 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 // device step counter bound by cfm_rng_bind (nullptr: seeds are used as passed); read by every
 // dropout kernel at run time so one captured HIP graph replays with fresh masks each step
 extern const uint64_t* g_rng_salt;
+// compute units of the current device (cached per device id; 256 if the query fails)
+int num_cus();
 }  // namespace cfm
 
 #define CFM_EXPORT extern "C" __attribute__((visibility("default")))

@@ -19,6 +19,17 @@ int check_launch(const char* what) {
 
 namespace cfm {
 const uint64_t* g_rng_salt = nullptr;
+
+int num_cus() {
+  static int cache[64];   // per device id; 0 = not asked yet (ids past the table are asked every time)
+  int dev = 0, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 256;
+  const bool slot = dev >= 0 && dev < 64;
+  if (slot && cache[dev]) return cache[dev];
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+  if (slot) cache[dev] = n;
+  return n;
+}
 }
 
 CFM_EXPORT int cfm_version(void) { return 1; }

@@ -36,7 +36,7 @@ def _ref(qkv, lens, B, T, H, dk, do):
     return o.detach(), x.grad.view(B * T, 3 * H * dk)
 
 
-@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("mode", [0, _lib.ATTN_MODE_TILED])
 @pytest.mark.parametrize("B,T,H", [(3, 373, 2), (2, 64, 4), (2, 97, 1)])
 def test_attention_vs_torch(attn_mode, mode, B, T, H):
     attn_mode(mode)
@@ -57,7 +57,7 @@ def test_attention_vs_torch(attn_mode, mode, B, T, H):
 @pytest.mark.parametrize("drop_p", [0.0, 0.1])
 def test_dq_from_stored_ds_matches_recompute(attn_mode, B, T, H, dk, lens, drop_p):
     """Whole-head backward: dQ from the dS^T the dK/dV kernel stores (default with the full workspace) against the
-    recomputing dQ kernel (cfm_attn_set_mode bit 10): dK / dV bit-identical (the same kernel, plus stores), dQ equal
+    recomputing dQ kernel (cfm_attn_set_mode ATTN_MODE_DQ_RECOMPUTE): dK / dV bit-identical (the same kernel, plus stores), dQ equal
     up to the bf16 rounding of the stored dS (the recomputing kernel rounds the same values, in another order);
     ragged lengths incl. a length-1 utterance and keys past len; dk 36 (Conformer-S); T 384 (Tq = T) and 130."""
     g = torch.Generator().manual_seed(T + dk + H)
@@ -66,7 +66,7 @@ def test_dq_from_stored_ds_matches_recompute(attn_mode, B, T, H, dk, lens, drop_
     do = torch.randn(B * T, H * dk, generator=g).to(DEV, torch.bfloat16)
     o, lse = ops.attn_fwd(qkv, lt, B, T, H, dk, drop_p=drop_p, seed=3)
     outs = []
-    for m in (1024, 0):
+    for m in (_lib.ATTN_MODE_DQ_RECOMPUTE, 0):
         attn_mode(m)
         dqkv, _, _, _ = ops.attn_bwd(qkv, o, do, lse, lt, B, T, H, dk, drop_p=drop_p, seed=3)
         outs.append(dqkv.float().view(B * T, 3, H * dk))
@@ -83,7 +83,7 @@ def test_attention_kernels_agree_under_dropout(attn_mode):
     lens = torch.tensor([T, 300], dtype=torch.int32, device=DEV)
     do = torch.randn(B * T, H * dk, generator=g).to(DEV, torch.bfloat16)
     outs = []
-    for mode in (0, 1):
+    for mode in (0, _lib.ATTN_MODE_TILED):
         attn_mode(mode)
         o, lse = ops.attn_fwd(qkv, lens, B, T, H, dk, drop_p=0.1, seed=9)
         dqkv, _, _, _ = ops.attn_bwd(qkv, o, do, lse, lens, B, T, H, dk, drop_p=0.1, seed=9)
@@ -179,11 +179,11 @@ def test_rel_attention_vs_torch(B, T, H, dk, lens):
 
 def test_rel_attention_mfma_matches_simt_under_dropout(attn_mode):
     """Same counter-based attention-dropout masks on both rel-pos paths: MFMA (default) and the SIMT kernels
-    (cfm_attn_set_mode bit 4), fwd + every gradient."""
+    (cfm_attn_set_mode ATTN_MODE_REL_SIMT), fwd + every gradient."""
     B, T, H, dk = 2, 150, 2, 64
     qkv, pos, pu, pv, do, ln = _rel_case(B, T, H, dk, [150, 111], 3)
     outs = []
-    for mode in (0, 16):
+    for mode in (0, _lib.ATTN_MODE_REL_SIMT):
         attn_mode(mode)
         o, lse = ops.attn_fwd(qkv, ln, B, T, H, dk, pos, pu, pv, drop_p=0.15, seed=77)
         g = ops.attn_bwd(qkv, o, do, lse, ln, B, T, H, dk, pos, pu, pv, drop_p=0.15, seed=77)
@@ -197,12 +197,12 @@ def test_rel_attention_mfma_matches_simt_under_dropout(attn_mode):
                                         (9, 130, 2, [130] * 8 + [77])])
 def test_rel_dpos_xcd_kernel_matches_round4(attn_mode, B, T, H, lens):
     """The round-5 dpos kernel (128 relative rows per workgroup, (b, h) pairs dealt to XCDs, dword-funnel band
-    loads, masks on edge tiles only) == the round-4 kernel (cfm_attn_set_mode bit 7) bit for bit: the same MFMA
+    loads, masks on edge tiles only) == the round-4 kernel (cfm_attn_set_mode ATTN_MODE_REL_DPOS_R4) bit for bit: the same MFMA
     k-steps over the same i order, the extra leading rows contribute exact zeros.  B*H = 18 pads the XCD deal."""
     dk = 64
     qkv, pos, pu, pv, do, ln = _rel_case(B, T, H, dk, lens, 5)
     outs = []
-    for mode in (0, 128):
+    for mode in (0, _lib.ATTN_MODE_REL_DPOS_R4):
         attn_mode(mode)
         o, lse = ops.attn_fwd(qkv, ln, B, T, H, dk, pos, pu, pv, drop_p=0.1, seed=11)
         outs.append(ops.attn_bwd(qkv, o, do, lse, ln, B, T, H, dk, pos, pu, pv, drop_p=0.1, seed=11)[1])
@@ -215,14 +215,14 @@ def test_rel_dpos_xcd_kernel_matches_round4(attn_mode, B, T, H, lens):
 @pytest.mark.parametrize("drop_p", [0.0, 0.1])
 def test_rel_dq_from_stored_ds_matches_recompute(attn_mode, B, T, H, lens, drop_p):
     """Rel-pos backward: dQ from the dS the dK/dV kernel stores (attn_rel_bwd_dqs_kernel, default; its band scatter is
-    explicit 2-byte LDS stores) against the recomputing dQ2 kernel (cfm_attn_set_mode bit 9): dK / dV and dpos
+    explicit 2-byte LDS stores) against the recomputing dQ2 kernel (cfm_attn_set_mode ATTN_MODE_REL_DQ_RECOMPUTE): dK / dV and dpos
     bit-identical (the same kernels), dQ and the u / v gradients equal up to the bf16 rounding of the stored dS;
     ragged lengths incl. a length-1 utterance, T 1498 (L60)."""
     dk = 64
     qkv, pos, pu, pv, do, ln = _rel_case(B, T, H, dk, lens, 13)
     o, lse = ops.attn_fwd(qkv, ln, B, T, H, dk, pos, pu, pv, drop_p=drop_p, seed=5)
     outs = []
-    for m in (512, 0):
+    for m in (_lib.ATTN_MODE_REL_DQ_RECOMPUTE, 0):
         attn_mode(m)
         dqkv, dpos, dpu, dpv = ops.attn_bwd(qkv, o, do, lse, ln, B, T, H, dk, pos, pu, pv, drop_p=drop_p, seed=5)
         outs.append((dqkv.float().view(B * T, 3, H * dk), dpos.float(), dpu.float(), dpv.float()))
@@ -251,7 +251,7 @@ def _keep(B, T, H, p, seed):
     return (half >= thr).reshape(B, H, T, T)
 
 
-@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("mode", [0, _lib.ATTN_MODE_TILED])
 @pytest.mark.parametrize("T,seed", [(64, 9), (63, (1 << 40) + 5), (37, 77)])
 def test_dropout_masks_read_back(attn_mode, mode, T, seed):
     """q = k = 0 makes P uniform (1 / T); V = identity rows makes o[i, j] = keep(i, j) / ((1 - p) T), and dO =

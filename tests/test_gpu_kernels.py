@@ -39,16 +39,24 @@ def test_gemm_layouts(dtype, ak, bk, M, N, K):
     assert _rel(C, ref) < tol
 
 
+def _forced(sel):
+    """cfm_gemm_set_mode value that forces one LDS-DMA pipeline variant (staged 256-row tiles off)"""
+    return _lib.GEMM_MODE_PIPE | sel << _lib.GEMM_MODE_SEL_SHIFT
+
+
 @pytest.fixture
 def gemm_mode():
     from nn_conformer_for_speech_recognition_amd import _lib
     yield lambda m: _lib.call("cfm_gemm_set_mode", m)
-    _lib.call("cfm_gemm_set_mode", 3)
+    _lib.call("cfm_gemm_set_mode", _lib.GEMM_MODE_DEFAULT)
 
 
 # register-staged / LDS-DMA auto / 256x128 BK64 / BK32 / 192x128 (K-major x K-major: warp-specialised, 8 compute
-# waves; + 524288: the shared-DMA 192-row pipeline) / 192x128 BK32 8 waves (AK only)
-@pytest.mark.parametrize("mode", [1, 2, 18, 34, 82, 82 | 524288, 114])
+# waves; | GEMM_MODE_KEEP_SHARED_DMA: the shared-DMA 192-row pipeline) / 192x128 BK32 8 waves (AK only)
+@pytest.mark.parametrize("mode", [_lib.GEMM_MODE_STAGED256, _lib.GEMM_MODE_PIPE, _forced(_lib.GEMM_SEL_PIPE256),
+                                  _forced(_lib.GEMM_SEL_PIPE256S), _forced(_lib.GEMM_SEL_192),
+                                  _forced(_lib.GEMM_SEL_192) | _lib.GEMM_MODE_KEEP_SHARED_DMA,
+                                  _forced(_lib.GEMM_SEL_PIPE192S8)])
 @pytest.mark.parametrize("ak,bk", [(True, True), (True, False), (False, True), (False, False)])
 @pytest.mark.parametrize("M,N,K", [(1000, 512, 512), (264, 136, 192), (520, 264, 1000), (8, 8, 64)])
 def test_gemm_kernel_variants(gemm_mode, mode, ak, bk, M, N, K):
@@ -70,7 +78,8 @@ def test_gemm_kernel_variants(gemm_mode, mode, ak, bk, M, N, K):
     assert _rel(C.float(), torch.nn.functional.silu(z)) < 1e-2
 
 
-@pytest.mark.parametrize("mode", [1, 18, 34, 82])
+@pytest.mark.parametrize("mode", [_lib.GEMM_MODE_STAGED256, _forced(_lib.GEMM_SEL_PIPE256),
+                                  _forced(_lib.GEMM_SEL_PIPE256S), _forced(_lib.GEMM_SEL_192)])
 def test_gemm_kernel_variants_splitk_batched(gemm_mode, mode):
     gemm_mode(mode)
     g = torch.Generator().manual_seed(17)
@@ -295,7 +304,7 @@ def test_conv2_bwd_data_pipeline(gemm_mode, B, F1, T1, C1, C2):
                                                output_padding=(F1 - (2 * F2 + 1), T1 - (2 * T2 + 1)))
     ref = ref.permute(0, 2, 3, 1)          # (B, F1, T1, C1)
     fast = ops.conv2_bwd_data(dh2.to(DEV), w2r.to(DEV), F1, T1)
-    gemm_mode(1)                           # no LDS-DMA pipeline: the register-staged gather kernel
+    gemm_mode(_lib.GEMM_MODE_STAGED256)     # no LDS-DMA pipeline: the register-staged gather kernel
     slow = ops.conv2_bwd_data(dh2.to(DEV), w2r.to(DEV), F1, T1)
     torch.cuda.synchronize()
     assert fast.shape == ref.shape
@@ -315,7 +324,7 @@ def test_conv2_fwd_pipeline(gemm_mode, B, F1, T1, C1, C2):
     ref = torch.nn.functional.conv2d(h1.double().permute(0, 3, 1, 2), W.double(), bias.double(), stride=2)
     ref = ref.permute(0, 3, 2, 1)         # (B, T2, F2, C2)
     fast = ops.conv2_fwd(h1.to(DEV), w2r.to(DEV), bias.to(DEV), torch.float32)
-    gemm_mode(1)
+    gemm_mode(_lib.GEMM_MODE_STAGED256)
     slow = ops.conv2_fwd(h1.to(DEV), w2r.to(DEV), bias.to(DEV), torch.float32)
     torch.cuda.synchronize()
     assert fast.shape == ref.shape
@@ -435,7 +444,7 @@ def test_wgrad_group_wide_tiles_vs_reference(M):
 @pytest.mark.parametrize("epi", ["bf16", "residual_drop", "rowdot", "batched"])
 def test_gemm_warp_specialised_matches_shared_dma(gemm_mode, M, K, epi):
     """The warp-specialised d-wide kernel (default for K-major x K-major GEMMs with <= 512 output columns) against
-    the shared-DMA 192-row pipeline (cfm_gemm_set_mode bit 19): the same 16x16x32 MFMAs in
+    the shared-DMA 192-row pipeline (cfm_gemm_set_mode GEMM_MODE_KEEP_SHARED_DMA): the same 16x16x32 MFMAs in
     the same k order and the same epilogue -> bit-identical outputs (ragged M, every epilogue the encoder uses:
     bf16 data gradients, fp32 residual-stream forwards with dropout + 0.5 scale, the rowdot of attention's D,
     batched overlapping-row operands as the front-end fold uses)."""
@@ -448,7 +457,7 @@ def test_gemm_warp_specialised_matches_shared_dma(gemm_mode, M, K, epi):
     with_ = torch.randn(M, N, generator=g).to(DEV, torch.bfloat16)
     T = M // 8 if M % 8 == 0 else M
     outs = []
-    for mode in (3, 3 | 524288):
+    for mode in (_lib.GEMM_MODE_DEFAULT, _lib.GEMM_MODE_DEFAULT | _lib.GEMM_MODE_KEEP_SHARED_DMA):
         gemm_mode(mode)
         if epi == "bf16":
             y = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
@@ -479,7 +488,7 @@ def test_gemm_warp_specialised_matches_shared_dma(gemm_mode, M, K, epi):
 @pytest.mark.parametrize("N", [1024, 1536, 640])
 def test_gemm_wide_ws_matches_pipe(gemm_mode, M, N):
     """1024- / 1536-wide K-major x K-major outputs (QKV, pointwise-conv-1 forward) run on the warp-specialised kernel;
-    cfm_gemm_set_mode bit 21 keeps the two-per-CU 192-row pipeline.  Same 16x16x32 MFMAs in the same k order and the
+    cfm_gemm_set_mode GEMM_MODE_KEEP_PIPE192 keeps the two-per-CU 192-row pipeline.  Same 16x16x32 MFMAs in the same k order and the
     same epilogue kinds -> bit-identical (bias-only and SiLU + pre-activation + dropout rows, ragged M)."""
     K = 512
     g = torch.Generator().manual_seed(M + N)
@@ -487,7 +496,7 @@ def test_gemm_wide_ws_matches_pipe(gemm_mode, M, N):
     w = (torch.randn(N, K, generator=g) * 0.05).to(DEV, torch.bfloat16)
     b = torch.randn(N, generator=g).to(DEV)
     outs = []
-    for mode in (3, 3 | 2097152):
+    for mode in (_lib.GEMM_MODE_DEFAULT, _lib.GEMM_MODE_DEFAULT | _lib.GEMM_MODE_KEEP_PIPE192):
         gemm_mode(mode)
         y = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
         ops.linear(x, w, b, out=y)
@@ -507,7 +516,7 @@ def test_gemm_wide_ws_matches_pipe(gemm_mode, M, N):
                                    ("plain", 512), ("silu_pre_drop", 512)])
 def test_gemm_fast_epilogue_matches_generic(gemm_mode, M, epi, N):
     """The compile-time epilogue kinds (epi_rows_fast: inputs issued ahead of the stores, bias loaded once) against
-    the generic per-row epilogue_store8 path (cfm_gemm_set_mode bit 14) on the same kernels: the same arithmetic in
+    the generic per-row epilogue_store8 path (cfm_gemm_set_mode GEMM_MODE_GENERIC_EPILOGUE) on the same kernels: the same arithmetic in
     the same order -> bit-identical outputs, for every kind the encoder launches, on the 256-row two-per-CU tiles
     (2048 wide), the 192-row tiles (1024 / 1536) and the warp-specialised d-wide kernel (512), ragged M."""
     K = 512
@@ -520,7 +529,7 @@ def test_gemm_fast_epilogue_matches_generic(gemm_mode, M, epi, N):
     with_ = torch.randn(M, N, generator=g).to(DEV, torch.bfloat16)
     T = M // 8 if M % 8 == 0 else M
     outs = []
-    for mode in (3, 3 | 16384):
+    for mode in (_lib.GEMM_MODE_DEFAULT, _lib.GEMM_MODE_DEFAULT | _lib.GEMM_MODE_GENERIC_EPILOGUE):
         gemm_mode(mode)
         if epi == "silu_pre_drop":
             y = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
@@ -638,7 +647,7 @@ def test_gemm_k_tail_pipeline(gemm_mode, M, N, K):
     res = torch.randn(M, N, generator=g).to(DEV)
     ref = x.double() @ w.double().T
     outs = {}
-    for mode in (3, 1):
+    for mode in (_lib.GEMM_MODE_DEFAULT, _lib.GEMM_MODE_STAGED256):
         gemm_mode(mode)
         y = torch.empty(M, N, device=DEV, dtype=torch.float32)
         ops.gemm(x, w, y, M, N, K)
@@ -652,7 +661,7 @@ def test_gemm_k_tail_pipeline(gemm_mode, M, N, K):
         assert _rel(y, ref) < 1e-5, mode
         assert _rel(yr, res.double() + 0.5 * (ref + b.double())) < 1e-5, mode
         assert _rel(yb.float(), ref) < 5e-3, mode
-    assert _rel(outs[3][0], outs[1][0]) < 1e-5
+    assert _rel(outs[_lib.GEMM_MODE_DEFAULT][0], outs[_lib.GEMM_MODE_STAGED256][0]) < 1e-5
 
 
 @pytest.mark.parametrize("D", [512, 144, 256, 100])
@@ -689,7 +698,7 @@ def test_layernorm_bf16_residual_input(D):
 @pytest.mark.parametrize("M,N,K", [(11936, 512, 2048), (11936, 512, 512), (3000, 144, 576), (777, 256, 1024)])
 def test_gemm_residual_epilogue_dtypes(gemm_mode, res_dt, out_dt, M, N, K):
     """The residual-add epilogue kinds (EF_F32_RES, EF_BF16_RES, EF_F32R_BF16): out = residual + out_scale *
-    dropout(x·wᵀ + b), bit-identical to the generic epilogue rows (cfm_gemm_set_mode bit 14) on the same main loop,
+    dropout(x·wᵀ + b), bit-identical to the generic epilogue rows (cfm_gemm_set_mode GEMM_MODE_GENERIC_EPILOGUE) on the same main loop,
     and within rounding of fp64."""
     g = torch.Generator().manual_seed(M + N + K)
     x = torch.randn(M, K, generator=g).to(DEV, torch.bfloat16)
@@ -697,7 +706,7 @@ def test_gemm_residual_epilogue_dtypes(gemm_mode, res_dt, out_dt, M, N, K):
     b = torch.randn(N, generator=g).to(DEV)
     res = torch.randn(M, N, generator=g).to(DEV, res_dt)
     outs = []
-    for mode in (3, 3 | 16384):
+    for mode in (_lib.GEMM_MODE_DEFAULT, _lib.GEMM_MODE_DEFAULT | _lib.GEMM_MODE_GENERIC_EPILOGUE):
         gemm_mode(mode)
         y = torch.empty(M, N, device=DEV, dtype=out_dt)
         ops.linear(x, w, b, out=y, drop_p=0.1, seed=11, out_scale=0.5, residual=res)
@@ -716,19 +725,19 @@ def test_gemm_residual_epilogue_dtypes(gemm_mode, res_dt, out_dt, M, N, K):
 def test_gemm_delta_epilogue(gemm_mode, M, N, K, drop_p, out_scale):
     """The residual module's output without the residual (EF_BF16_DELTA: bf16 out_scale * dropout(x·wᵀ + b), the
     RES_FUSE form whose add the next LayerNorm does): bit-identical to the generic epilogue rows (cfm_gemm_set_mode
-    bit 14) on the same main loop, and equal to the fp32 residual epilogue's output minus its residual up to the
+    GEMM_MODE_GENERIC_EPILOGUE) on the same main loop, and equal to the fp32 residual epilogue's output minus its residual up to the
     bf16 rounding of the delta (same dropout mask)."""
     g = torch.Generator().manual_seed(M + N + K)
     x = torch.randn(M, K, generator=g).to(DEV, torch.bfloat16)
     w = (torch.randn(N, K, generator=g) * 0.05).to(DEV, torch.bfloat16)
     b = torch.randn(N, generator=g).to(DEV)
     outs = []
-    for mode in (3, 3 | 16384):
+    for mode in (_lib.GEMM_MODE_DEFAULT, _lib.GEMM_MODE_DEFAULT | _lib.GEMM_MODE_GENERIC_EPILOGUE):
         gemm_mode(mode)
         y = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
         ops.linear(x, w, b, out=y, drop_p=drop_p, seed=11, out_scale=out_scale)
         outs.append(y.clone())
-    gemm_mode(3)
+    gemm_mode(_lib.GEMM_MODE_DEFAULT)
     zero = torch.zeros(M, N, device=DEV)
     yr = torch.empty(M, N, device=DEV)
     ops.linear(x, w, b, out=yr, drop_p=drop_p, seed=11, out_scale=out_scale, residual=zero)
@@ -772,7 +781,7 @@ def test_layernorm_fwd_residual_add(D, dd):
 @pytest.mark.parametrize("res", [False, True])
 def test_gemm_ws96_narrow_outputs(gemm_mode, M, K, res):
     """256-wide outputs (Conformer-M's d) on the 96-row warp-specialised tiles (250 tiles at M 11,936 where 192-row
-    tiles give 126) against the 192-row warp-specialised kernel (cfm_gemm_set_mode bit 23): the same 16x16x32 MFMAs
+    tiles give 126) against the 192-row warp-specialised kernel (cfm_gemm_set_mode GEMM_MODE_KEEP_WS192): the same 16x16x32 MFMAs
     in the same k order and the same epilogue -> bit-identical, bf16 data-gradient and fp32 residual epilogues."""
     N = 256
     g = torch.Generator().manual_seed(M + K + res)
@@ -781,7 +790,7 @@ def test_gemm_ws96_narrow_outputs(gemm_mode, M, K, res):
     b = torch.randn(N, generator=g).to(DEV)
     r = torch.randn(M, N, generator=g).to(DEV)
     outs = []
-    for mode in (3, 3 | 8388608):
+    for mode in (_lib.GEMM_MODE_DEFAULT, _lib.GEMM_MODE_DEFAULT | _lib.GEMM_MODE_KEEP_WS192):
         gemm_mode(mode)
         if res:
             y = torch.empty(M, N, device=DEV, dtype=torch.float32)
