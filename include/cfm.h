@@ -384,6 +384,28 @@ int cfm_layernorm_bwd_drop(const void* dy, int dtdy, const void* x, int dtx, con
                            int dtdx, float* dgamma, float* dbeta, float* ws, long M, int D, void* g2,
                            float g2_scale, float g2_p, uint64_t g2_seed, void* stream);
 
+/* Two LayerNorms back to back (an encoder layer's final_layer_norm followed by the next layer's ffn1 LayerNorm) as one
+   kernel per direction.  Forward: y = LN(x; gamma1, beta1) (fp32) and z = LN(y; gamma2, beta2) (dtype_z), with both
+   rows of statistics -- y, z and the statistics are bit-identical to two cfm_layernorm_fwd calls, and y is never read
+   back.  Backward: dz (dtype_dz) is the gradient of z, dres (fp32, nullable) the gradient reaching y directly;
+   dx = LN1'(dres + LN2'(dz)) with y recomputed from x, g2 as cfm_layernorm_bwd_drop's.  dgb1 / dgb2: [dgamma | dbeta]
+   (2*D floats each) of the first / second LayerNorm; NULL leaves that pair's partial rows in ws for the caller to
+   reduce -- nb = ws_bytes / (16*D) rows of 2*D floats for the first pair at ws, the same for the second at
+   ws + nb*2*D.
+   cfm_layernorm_pair_ok: 1 when fused kernels exist for width D and dtype_z (D 512, 256, and the lane-group widths
+   D % 8 == 0, D < 512, D != 128), else 0 -- then make the two calls; pure host logic, no GPU API.  All pointers 16-B
+   aligned. */
+int cfm_layernorm_pair_ok(int D, int dtype_z);
+size_t cfm_layernorm_fwd_pair_ws_bytes(long M, int D);   /* 0: the forward needs no workspace */
+int cfm_layernorm_fwd_pair(const float* x, const float* gamma1, const float* beta1, const float* gamma2,
+                           const float* beta2, float* y, void* z, int dtype_z, float* mean1, float* rstd1,
+                           float* mean2, float* rstd2, long M, int D, float eps, void* stream);
+size_t cfm_layernorm_bwd_pair_ws_bytes(long M, int D);
+int cfm_layernorm_bwd_pair(const void* dz, int dtype_dz, const float* dres, const float* x, const float* gamma1,
+                           const float* beta1, const float* mean1, const float* rstd1, const float* gamma2,
+                           const float* mean2, const float* rstd2, float* dx, float* dgb1, float* dgb2, float* ws,
+                           long M, int D, void* g2, float g2_scale, float g2_p, uint64_t g2_seed, void* stream);
+
 /* y = act(x*scale [dropout]) + residual, elementwise helpers used at residual joins. */
 int cfm_scale_dropout(const void* x, int dtype_x, void* y, int dtype_y, long n, float scale,
                       float drop_p, uint64_t seed, uint64_t offset, void* stream);

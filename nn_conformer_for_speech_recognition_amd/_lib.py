@@ -156,6 +156,12 @@ _SIGS = {
     "cfm_layernorm_bwd_drop": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p,
                                        c_float, c_float, c_u64, c_void_p]),
+    "cfm_layernorm_pair_ok": (c_int, [c_int, c_int]),
+    "cfm_layernorm_fwd_pair_ws_bytes": (c_size_t, [c_long, c_int]),
+    "cfm_layernorm_fwd_pair": (c_int, [c_void_p] * 7 + [c_int] + [c_void_p] * 4 + [c_long, c_int, c_float, c_void_p]),
+    "cfm_layernorm_bwd_pair_ws_bytes": (c_size_t, [c_long, c_int]),
+    "cfm_layernorm_bwd_pair": (c_int, [c_void_p, c_int] + [c_void_p] * 13 + [c_long, c_int, c_void_p, c_float, c_float,
+                                                                          c_u64, c_void_p]),
     "cfm_scale_dropout": (c_int, [c_void_p, c_int, c_void_p, c_int, c_long, c_float, c_float, c_u64, c_u64,
                                   c_void_p]),
     "cfm_convmod_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),

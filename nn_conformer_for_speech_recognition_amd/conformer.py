@@ -114,6 +114,14 @@ RES_BF16 = os.environ.get("CFM_RES_BF16", "0") == "1"
 # LayerNorms grow 8.4 -> 15.5 us: the unfused LayerNorm reads the stream the GEMM has just written from the Infinity
 # Cache, the fused one reads the older x.  L15 18.7 -> 19.0 ms, so the epilogue form stays the default.
 RES_FUSE = os.environ.get("CFM_RES_FUSE", "0") == "1"
+# CFM_LN_PAIR (default on; 0: the two-call form, A/B and tests): final_layer_norm of layer i and the ffn1 LayerNorm of
+# layer i + 1 run back to back with nothing between them, so the encoder runs them as ONE kernel per direction
+# (ops.layernorm_fwd_pair / layernorm_bwd_pair): layer i's node also returns the next layer's normalised input and,
+# in backward, takes its gradient; the fp32 stream between the layers is written once and not read back, and the
+# gradient of that stream is never materialised.  Same values as the two-call form (forward bit for bit).  Off where
+# no fused kernel exists (ops.layernorm_pair_ok), under RES_FUSE / RES_BF16, with the MX fp8 LayerNorm copy (fp8=True),
+# and for a layer called on its own.
+LN_PAIR = os.environ.get("CFM_LN_PAIR", "1") != "0"
 
 
 class _Cfg:
@@ -247,10 +255,14 @@ def _fp8_linear(x, cfg, i, xq=None, **kw):
     return ops.linear(xq, wq, x_scale=sx, w_scale=sw, **kw)
 
 
-def _ffn_fwd(x, P, o, cfg, seed, d=None):
-    """-> (the new stream, or the bf16 module output under RES_FUSE; saved tensors; the module input)"""
+def _ffn_fwd(x, P, o, cfg, seed, d=None, xn=None):
+    """-> (the new stream, or the bf16 module output under RES_FUSE; saved tensors; the module input).
+    xn: the module-input LayerNorm's output when the layer below already computed it (LN_PAIR)."""
     cd = cfg.cd
-    xn, xq, mu, rs, x = _ln_fwd(x, P, o, cfg, o + 2, d)
+    if xn is not None:
+        xq = mu = rs = None
+    else:
+        xn, xq, mu, rs, x = _ln_fwd(x, P, o, cfg, o + 2, d)
     w1, w2 = _w(P[o + 2], cd), _w(P[o + 4], cd)
     pre = torch.empty(x.shape[0], cfg.ffn, device=x.device, dtype=cd)
     # MX fp8 for both FFN GEMMs: the up-projection's epilogue also writes the MX copy of h (the down GEMM's operand)
@@ -302,6 +314,11 @@ def _ffn_bwd(g, x, sv, P, o, cfg, seed, grads, side, g2=None, nxt=None):
     da = ops.linear_dgrad(g2, w2, pre=pre, act_grad=True, drop_p=cfg.p, seed=seed, wt=_wt(cfg, o + 4))
     grads[o + 2], grads[o + 3] = _wgrad_bias(side, da, xn, o + 2)
     dxn = ops.linear_dgrad(da, w1, wt=_wt(cfg, o + 2))
+    if mu is None:
+        # the module-input LayerNorm ran in the layer below (LN_PAIR) and so does its backward: hand it the stream
+        # gradient and the gradient of the normalised input apart
+        _chk(f"ffn{o}_bwd", g2, da, dxn)
+        return g, dxn
     dx, grads[o], grads[o + 1], g2n = _ln_bwd(dxn, x, P, o, mu, rs, g, side, nxt)
     _chk(f"ffn{o}_bwd", g2, da, dxn, dx, g2n)
     return dx, g2n
@@ -424,7 +441,9 @@ class _ConformerLayerFn(torch.autograd.Function):
     """One torchaudio ConformerLayer as a single autograd node over libcfm."""
 
     @staticmethod
-    def forward(ctx, x, lens, cfg, *params):
+    def forward(ctx, x, lens, cfg, xn_in, ng, nb, *params):
+        """xn_in: this layer's ffn1 LayerNorm output, computed by the layer below; ng, nb: the ffn1 LayerNorm weight
+        and bias of the layer above, whose output this layer then returns beside its own (LN_PAIR; None: plain)."""
         P = list(params[:len(_PNAMES)])
         R = params[len(_PNAMES):]
         if cfg.shadow is not None:       # compute-dtype copies refreshed by Conformer (one launch)
@@ -438,7 +457,7 @@ class _ConformerLayerFn(torch.autograd.Function):
         x0 = x
         # each module returns its output (the new stream; under RES_FUSE the pending bf16 module output, added by the
         # next LayerNorm) and its input, materialised by that LayerNorm -- the tensors the backward saves
-        y1, sv1, _ = _ffn_fwd(x0, P, 0, cfg, s)
+        y1, sv1, _ = _ffn_fwd(x0, P, 0, cfg, s, xn=xn_in)
         step = (lambda xin, y: (xin, y)) if cfg.rfuse else (lambda xin, y: (y, None))
         cur = step(x0, y1)
         if cfg.conv_first:
@@ -455,23 +474,38 @@ class _ConformerLayerFn(torch.autograd.Function):
             chain = (x1, xa)
         y4, sv4, x3 = _ffn_fwd(cur[0], P, 22, cfg, s + 30, cur[1])
         cur = step(x3, y4)
+        pair = ()
         if cur[1] is not None:
             x4, out, mu5, rs5 = ops.layernorm_fwd_res(cur[0], cur[1], P[28], P[29], _EPS, out_dtype=torch.float32)
+        elif ng is not None:
+            x4 = cur[0]
+            out, xn_next, mu5, rs5, mu6, rs6 = ops.layernorm_fwd_pair(x4, P[28], P[29], ng, nb, _EPS, out_dtype=cfg.cd)
+            pair = (ng, nb, mu6, rs6)
         else:
             x4 = cur[0]
             out, mu5, rs5 = ops.layernorm_fwd(x4, P[28], P[29], _EPS, out_dtype=torch.float32)
         _chk(f"layer{cfg.layer_index}_fwd_out", out, mu5, rs5)
         ctx.cfg = cfg
         ctx.sv = (sv1, sva, svc, sv4)
-        ctx.save_for_backward(x0, chain[0], chain[1], x3, x4, mu5, rs5, lens, *params)
+        ctx.nparams = len(params)
+        ctx.pair_out = bool(pair)
+        ctx.save_for_backward(x0, chain[0], chain[1], x3, x4, mu5, rs5, lens, *params, *pair)
+        if pair:
+            ctx.set_materialize_grads(False)    # a missing gradient of xn_next selects the plain backward
+            return out, xn_next
         return out
 
     @staticmethod
-    def backward(ctx, gout):
+    def backward(ctx, gout, gxn=None):
         cfg = ctx.cfg
         saved = ctx.saved_tensors
         x0, c0, c1, x3, x4, mu5, rs5, lens = saved[:8]
-        params = saved[8:]
+        params = saved[8:8 + ctx.nparams]
+        ng = nb = mu6 = rs6 = None
+        if ctx.pair_out:
+            ng, nb, mu6, rs6 = saved[8 + ctx.nparams:]
+            if gout is None:
+                gout = torch.zeros_like(x4)
         P = params[:len(_PNAMES)]
         R = params[len(_PNAMES):]
         sv1, sva, svc, sv4 = ctx.sv
@@ -483,7 +517,9 @@ class _ConformerLayerFn(torch.autograd.Function):
         # defer this layer's weight-gradient GEMMs into the encoder-wide grouped launch (flushed by layer 0,
         # the last to run backward) when no parameter accumulates into an existing .grad
         # (never when a parameter carries a gradient hook: hooks fire as .grad lands, before the flush)
-        if cfg.group_wgrad and all(p.grad is None and not _has_grad_hooks(p) for p in params):
+        # (LN_PAIR: this node also produces the ffn1 LayerNorm gradients of the layer above)
+        owned = params if gxn is None else (*params, ng, nb)
+        if cfg.group_wgrad and all(p.grad is None and not _has_grad_hooks(p) for p in owned):
             side.group = _WGRAD_GROUPS.setdefault(str(gout.device), ops.WgradGroup())
             side.group.arm_final_flush()
             side.dest = cfg.grad_dest
@@ -495,7 +531,13 @@ class _ConformerLayerFn(torch.autograd.Function):
         conv_in, mha_in, ffn1_in = _in_drop("conv", cfg, s + 10), _in_drop("mha", cfg, s + 20), _in_drop("ffn", cfg, s)
         if "lndrop" in ops.DISABLED:
             ffn2_in = conv_in = mha_in = ffn1_in = None
-        if ffn2_in is None:
+        dng = dnb = None
+        if gxn is not None:
+            # both LayerNorms of the layer boundary in one kernel: gout reaches the stream directly, gxn through the
+            # upper layer's ffn1 LayerNorm
+            g, (grads[28], grads[29]), (dng, dnb), g2 = ops.layernorm_bwd_pair(
+                gxn.contiguous(), gout, x4, P[28], P[29], mu5, rs5, ng, mu6, rs6, side=side, drop=ffn2_in)
+        elif ffn2_in is None:
             (g, grads[28], grads[29]), g2 = ops.layernorm_bwd(gout, x4, P[28], mu5, rs5, side=side), None
         else:
             g, grads[28], grads[29], g2 = ops.layernorm_bwd(gout, x4, P[28], mu5, rs5, side=side, drop=ffn2_in)
@@ -507,7 +549,8 @@ class _ConformerLayerFn(torch.autograd.Function):
             g, g2 = _ffn_bwd(g, x3, sv4, P, 22, cfg, s + 30, grads, side, g2, conv_in)
             g, g2 = _conv_bwd(g, c1, svc, P, cfg, s + 10, grads, side, g2, mha_in)
             g, g2 = _mha_bwd(g, c0, sva, P, R, cfg, s + 20, lens, grads, rgrads, side, g2, ffn1_in)
-        g, _ = _ffn_bwd(g, x0, sv1, P, 0, cfg, s, grads, side, g2, None)
+        # (with the ffn1 LayerNorm run by the layer below: g is the stream gradient, gxn_in that of the normalised input)
+        g, gxn_in = _ffn_bwd(g, x0, sv1, P, 0, cfg, s, grads, side, g2, None)
         side.join()
         if cfg.on_routed is not None and side.dest and side.routed == len(side.dest):
             cfg.on_routed(cfg.layer_index)       # (data-parallel reducer: this layer's buckets are final at flush)
@@ -524,7 +567,7 @@ class _ConformerLayerFn(torch.autograd.Function):
                 cfg.on_flushed(cfg.layer_index)
         _chk(f"layer{cfg.layer_index}_bwd_dx", g)
         ctx.sv = None
-        return (g, None, None, *grads, *rgrads)
+        return (g, None, None, gxn_in, dng, dnb, *grads, *rgrads)
 
 
 class ConformerLayer(nn.Module):
@@ -556,10 +599,12 @@ class ConformerLayer(nn.Module):
 
     def forward_tokens(self, x, lens_i32, B, T, compute_dtype, seed, pe=None, shadow=None, layer_index=0,
                        group_wgrad=False, grad_dest=None, flush_here=False, on_flushed=None, sync_bn=None,
-                       count_batches=True, on_routed=None, pos_pre=None):
+                       count_batches=True, on_routed=None, pos_pre=None, xn_in=None, next_ln=None):
         """x: (B*T, d) fp32 token-major; lens_i32: (B,) int32 on the device; shadow: optional
         ({param index: compute-dtype copy}, {param index: its transposed K-major copy}) of this
-        layer's weight matrices (see Conformer._shadows)."""
+        layer's weight matrices (see Conformer._shadows).
+        LN_PAIR (Conformer.forward_tokens): xn_in is this layer's ffn1 LayerNorm output from the layer below;
+        next_ln = (weight, bias) of the next layer's ffn1 LayerNorm -> returns (out, that LayerNorm's output)."""
         cfg = _Cfg()
         cfg.shadow = shadow
         cfg.B, cfg.T, cfg.d, cfg.H, cfg.ffn, cfg.K = B, T, self.d, self.H, self.ffn, self.K
@@ -582,7 +627,8 @@ class ConformerLayer(nn.Module):
         cfg.sync_bn = sync_bn
         if count_batches and self.training and bn.track_running_stats:
             bn.num_batches_tracked.add_(1)
-        return _ConformerLayerFn.apply(x, lens_i32, cfg, *self.params())
+        ng, nb = next_ln if next_ln is not None else (None, None)
+        return _ConformerLayerFn.apply(x, lens_i32, cfg, xn_in, ng, nb, *self.params())
 
 
 class Conformer(nn.Module):
@@ -720,6 +766,17 @@ class Conformer(nn.Module):
         self.sync_bn = (lambda t: dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group), world)
         return self
 
+    def _ln_pair(self):
+        """LN_PAIR for this encoder: fused kernels for its width and compute dtype, the plain fp32 stream, no MX fp8
+        copy out of the ffn1 LayerNorm, 16-B aligned LayerNorm parameters."""
+        bf = self.compute_dtype == torch.bfloat16
+        if not LN_PAIR or self.fp8 or (bf and (RES_FUSE or RES_BF16)):
+            return False
+        if not ops.layernorm_pair_ok(self.input_dim, self.compute_dtype):
+            return False
+        lns = [m for ly in self.conformer_layers for m in (ly.final_layer_norm, ly.ffn1.sequential[0])]
+        return all(t.dtype == torch.float32 and t.data_ptr() % 16 == 0 for m in lns for t in (m.weight, m.bias))
+
     def forward_tokens(self, x, lens_i32, B, T, seed=None):
         if torch.compiler.is_compiling():
             return self._forward_tokens_ops(x, lens_i32, B, T, seed)
@@ -736,13 +793,18 @@ class Conformer(nn.Module):
         # grouped weight gradients need layer 0 to run backward last (it flushes the group): true for the
         # sequential encoder; deferral is per layer and falls back when a .grad accumulates
         group = self.compute_dtype == torch.bfloat16
+        pair = self._ln_pair()
+        xn = None
         for i, layer in enumerate(self.conformer_layers):
+            nxt = self.conformer_layers[i + 1].ffn1.sequential[0] if pair and i + 1 < len(self.conformer_layers) else None
             x = layer.forward_tokens(x, lens_i32, B, T, self.compute_dtype, seed + 100 * i, pe, shadows[i],
                                      layer_index=i, group_wgrad=group,
                                      grad_dest=self.grad_dest[i] if self.grad_dest else None,
                                      flush_here=i in self.flush_layers, on_flushed=self.on_flushed,
                                      sync_bn=self.sync_bn, count_batches=False, on_routed=self.on_routed,
-                                     pos_pre=None if pos_all is None else pos_all[i])
+                                     pos_pre=None if pos_all is None else pos_all[i], xn_in=xn,
+                                     next_ln=None if nxt is None else (nxt.weight, nxt.bias))
+            x, xn = x if nxt is not None else (x, None)
         # every layer's BatchNorm num_batches_tracked += 1 in one multi-tensor launch (not one per layer)
         counters = [ly.conv_module.sequential[3].num_batches_tracked for ly in self.conformer_layers
                     if self.training and ly.conv_module.sequential[3].track_running_stats]

@@ -429,6 +429,384 @@ __global__ __launch_bounds__(256) void ln_bwd_grp(const TDY* __restrict__ dy, co
   }
 }
 
+// ---------------------------------------------------------------- LayerNorm pairs (layer boundary)
+// final_layer_norm of encoder layer i followed directly by the ffn1 LayerNorm of layer i + 1: y = LN(x; g1, b1) is the
+// fp32 stream between the layers, z = LN(y; g2, b2) the next layer's first GEMM operand.  One kernel per direction
+// instead of two: the forward keeps y in registers (no fp32 write-then-read), the backward recomputes y from x and
+// never materialises the gradient of y.  The expressions and the reduction order are those of ln_fwd_vec /
+// ln_fwd_grp, so y, z and the statistics equal the two-call path's bit for bit.
+template <int V, typename TZ>
+__global__ __launch_bounds__(256) void ln_fwd_pair_vec(const float* __restrict__ x, const float* __restrict__ gamma1,
+                                                       const float* __restrict__ beta1,
+                                                       const float* __restrict__ gamma2,
+                                                       const float* __restrict__ beta2, float* __restrict__ y,
+                                                       TZ* __restrict__ z, float* __restrict__ mean1,
+                                                       float* __restrict__ rstd1, float* __restrict__ mean2,
+                                                       float* __restrict__ rstd2, long M, float eps) {
+  constexpr int D = 64 * V, R = LN_FWD_ROWS;
+  const int lane = threadIdx.x & 63;
+  const long row0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * R;
+  if (row0 >= M) return;
+  float v[R][V], g[V], b[V];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (row0 + r < M) {
+      ldv<V>(x + (row0 + r) * D + lane * V, v[r]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < V; ++i) v[r][i] = 0.f;
+    }
+  }
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    ldv<V>((pass ? gamma2 : gamma1) + lane * V, g);
+    ldv<V>((pass ? beta2 : beta1) + lane * V, b);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < V; ++i) s += v[r][i];
+      const float mean = wave_sum(s) * (1.f / D);
+      float q = 0.f;
+#pragma unroll
+      for (int i = 0; i < V; ++i) {
+        v[r][i] -= mean;
+        q += v[r][i] * v[r][i];
+      }
+      const float rstd = rsqrtf(wave_sum(q) * (1.f / D) + eps);
+      if (row0 + r < M) {    // wave-uniform (a row past M stays all zero through both passes)
+#pragma unroll
+        for (int i = 0; i < V; ++i) v[r][i] = v[r][i] * rstd * g[i] + b[i];
+        if (pass == 0) stv<V>(y + (row0 + r) * D + lane * V, v[r]);
+        else stv<V>(z + (row0 + r) * D + lane * V, v[r]);
+        if (lane == 0) {
+          (pass ? mean2 : mean1)[row0 + r] = mean;
+          (pass ? rstd2 : rstd1)[row0 + r] = rstd;
+        }
+      }
+    }
+  }
+}
+
+template <int G, typename TZ>
+__global__ __launch_bounds__(256) void ln_fwd_pair_grp(const float* __restrict__ x, const float* __restrict__ gamma1,
+                                                       const float* __restrict__ beta1,
+                                                       const float* __restrict__ gamma2,
+                                                       const float* __restrict__ beta2, float* __restrict__ y,
+                                                       TZ* __restrict__ z, float* __restrict__ mean1,
+                                                       float* __restrict__ rstd1, float* __restrict__ mean2,
+                                                       float* __restrict__ rstd2, long M, int D, float eps) {
+  constexpr int RPW = 64 / G, R = LN_FWD_ROWS;
+  const int lane = threadIdx.x & 63, j = lane % G, c = 8 * j;
+  const bool act = c < D;
+  const long row0 = (((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + lane / G) * R;
+  float v[R][8], g[8], b[8];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (act && row0 + r < M) {
+      ldv<8>(x + (row0 + r) * D + c, v[r]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v[r][i] = 0.f;
+    }
+  }
+  const float invd = 1.f / (float)D;
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass) {
+      // the second LayerNorm takes y as ln_fwd_grp does: 16-B loads (of this lane's own stores just above, from the
+      // cache -- still no pass over memory) through a pointer the compiler cannot trace back to them.  Fed from the
+      // registers it contracts (v - sum / D) and the squares differently per element than ln_fwd_grp, and rstd2
+      // comes out an ulp off the two-call path
+      const float* yr = y;
+      asm volatile("" : "+s"(yr) : : "memory");
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if (act && row0 + r < M) {
+          ldv<8>(yr + (row0 + r) * D + c, v[r]);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) v[r][i] = 0.f;
+        }
+      }
+    }
+    if (act) {
+      ldv<8>((pass ? gamma2 : gamma1) + c, g);
+      ldv<8>((pass ? beta2 : beta1) + c, b);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) s += v[r][i];
+      const float mean = group_sum<G>(s) * invd;
+      float q = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        v[r][i] = act ? v[r][i] - mean : 0.f;
+        q += v[r][i] * v[r][i];
+      }
+      const float rstd = rsqrtf(group_sum<G>(q) * invd + eps);
+      if (row0 + r < M) {
+        if (act) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) v[r][i] = v[r][i] * rstd * g[i] + b[i];
+          if (pass == 0) stv<8>(y + (row0 + r) * D + c, v[r]);
+          else stv<8>(z + (row0 + r) * D + c, v[r]);
+        }
+        if (j == 0) {
+          (pass ? mean2 : mean1)[row0 + r] = mean;
+          (pass ? rstd2 : rstd1)[row0 + r] = rstd;
+        }
+      }
+    }
+  }
+}
+
+// Backward of the pair.  dz: gradient of z; dres: the gradient reaching y down the residual path (nullable).
+//   xh = (x - m1) r1, y = xh g1 + b1, yh = (y - m2) r2, gz = dz g2
+//   dy = dres + r2 (gz - mean(gz) - yh mean(gz yh)),  gy = dy g1,  dx = r1 (gy - mean(gy) - xh mean(gy xh))
+// Column partials: [dg1 | db1] = [dy xh | dy] in the first nb x 2D block of ws, [dg2 | db2] = [dz yh | dz] in the second
+// (each block laid out as ln_bwd_vec's, so each is one task of the grouped column reduction).  The next row's dz and x
+// loads are issued before this row's reductions: the two dependent reduction stages would otherwise leave a wave with
+// nothing in flight for twice as long as ln_bwd_vec does.
+template <int V, typename TDZ>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void ln_bwd_pair_vec(const TDZ* __restrict__ dz, const float* __restrict__ dres,
+                                                       const float* __restrict__ x, const float* __restrict__ gamma1,
+                                                       const float* __restrict__ beta1,
+                                                       const float* __restrict__ mean1,
+                                                       const float* __restrict__ rstd1,
+                                                       const float* __restrict__ gamma2,
+                                                       const float* __restrict__ mean2,
+                                                       const float* __restrict__ rstd2, float* __restrict__ dx,
+                                                       float* __restrict__ ws, long M, LnDrop dr) {
+  if (dr.g2 && dr.p > 0.f) dr.seed = salted_seed(dr.seed, dr.salt);
+  constexpr int D = 64 * V;
+  __shared__ float red[4][2 * D];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int wglob = blockIdx.x * 4 + wv;
+  const int nwaves = gridDim.x * 4;
+  float ga[V], ba[V], gb[V], pg1[V], pb1[V], pg2[V], pb2[V];
+  ldv<V>(gamma1 + lane * V, ga);
+  ldv<V>(beta1 + lane * V, ba);
+  ldv<V>(gamma2 + lane * V, gb);
+#pragma unroll
+  for (int i = 0; i < V; ++i) pg1[i] = pb1[i] = pg2[i] = pb2[i] = 0.f;
+  float d[V], xh[V], st[4];
+  auto fetch = [&](long row, float (&fd)[V], float (&fx)[V], float (&fs)[4]) {
+    fs[0] = mean1[row]; fs[1] = rstd1[row]; fs[2] = mean2[row]; fs[3] = rstd2[row];
+    ldv<V>(dz + row * D + lane * V, fd);
+    ldv<V>(x + row * D + lane * V, fx);
+  };
+  long row = wglob;
+  if (row < M) fetch(row, d, xh, st);
+  while (row < M) {
+    const long nrow = row + nwaves;
+    float o[V], nd[V], nx[V], nst[4];
+    if (dres) ldv<V>(dres + row * D + lane * V, o);   // (needed after the first reduction stage)
+    else {
+#pragma unroll
+      for (int i = 0; i < V; ++i) o[i] = 0.f;
+    }
+    if (nrow < M) fetch(nrow, nd, nx, nst);
+    const float m1 = st[0], r1 = st[1], m2 = st[2], r2 = st[3];
+    float yh[V], gz[V];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      xh[i] = (xh[i] - m1) * r1;
+      yh[i] = (xh[i] * ga[i] + ba[i] - m2) * r2;
+      gz[i] = d[i] * gb[i];
+      pg2[i] += d[i] * yh[i];
+      pb2[i] += d[i];
+      s1 += gz[i];
+      s2 += gz[i] * yh[i];
+    }
+    s1 = wave_sum(s1) * (1.f / D);
+    s2 = wave_sum(s2) * (1.f / D);
+    float t1 = 0.f, t2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      o[i] += r2 * (gz[i] - s1 - yh[i] * s2);    // dy
+      gz[i] = o[i] * ga[i];                      // gy
+      pg1[i] += o[i] * xh[i];
+      pb1[i] += o[i];
+      t1 += gz[i];
+      t2 += gz[i] * xh[i];
+    }
+    t1 = wave_sum(t1) * (1.f / D);
+    t2 = wave_sum(t2) * (1.f / D);
+#pragma unroll
+    for (int i = 0; i < V; ++i) o[i] = r1 * (gz[i] - t1 - xh[i] * t2);
+    stv<V>(dx + row * D + lane * V, o);
+    if constexpr (V == 8) {
+      if (dr.g2) {   // the module below's input gradient: bf16(dx * scale * dropout mask), as ln_bwd_vec
+        float sc[8];
+        if (dr.p > 0.f) dropout_scale8(dr.p, dr.seed, (uint64_t)(row * D + lane * V), sc);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sc[i] = dr.p > 0.f ? dr.scale * sc[i] : dr.scale;
+        float q[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) q[i] = o[i] * sc[i];
+        st8_dyn(dr.g2, CFM_BF16, row * D + lane * V, q);
+      }
+    }
+    if (nrow < M) {
+#pragma unroll
+      for (int i = 0; i < V; ++i) {
+        d[i] = nd[i];
+        xh[i] = nx[i];
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) st[i] = nst[i];
+    }
+    row = nrow;
+  }
+  // one LDS block serves both partial pairs in turn
+#pragma unroll
+  for (int blk = 0; blk < 2; ++blk) {
+    if (blk) __syncthreads();
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      red[wv][lane * V + i] = blk ? pg2[i] : pg1[i];
+      red[wv][D + lane * V + i] = blk ? pb2[i] : pb1[i];
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < 2 * D; c += 256)
+      ws[((long)blk * gridDim.x + blockIdx.x) * 2 * D + c] = red[0][c] + red[1][c] + red[2][c] + red[3][c];
+  }
+}
+
+template <int G, typename TDZ>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void ln_bwd_pair_grp(const TDZ* __restrict__ dz, const float* __restrict__ dres,
+                                                       const float* __restrict__ x, const float* __restrict__ gamma1,
+                                                       const float* __restrict__ beta1,
+                                                       const float* __restrict__ mean1,
+                                                       const float* __restrict__ rstd1,
+                                                       const float* __restrict__ gamma2,
+                                                       const float* __restrict__ mean2,
+                                                       const float* __restrict__ rstd2, float* __restrict__ dx,
+                                                       float* __restrict__ ws, long M, int D, LnDrop dr) {
+  if (dr.g2 && dr.p > 0.f) dr.seed = salted_seed(dr.seed, dr.salt);
+  constexpr int RPW = 64 / G;
+  __shared__ float red[4][2 * 8 * G];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane % G, c = 8 * j;
+  const bool act = c < D;
+  const long slot = ((long)blockIdx.x * 4 + wv) * RPW + lane / G;
+  const long nslots = (long)gridDim.x * 4 * RPW;
+  float ga[8], ba[8], gb[8], pg1[8], pb1[8], pg2[8], pb2[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ga[i] = ba[i] = gb[i] = pg1[i] = pb1[i] = pg2[i] = pb2[i] = 0.f;
+  if (act) {
+    ldv<8>(gamma1 + c, ga);
+    ldv<8>(beta1 + c, ba);
+    ldv<8>(gamma2 + c, gb);
+  }
+  const float invd = 1.f / (float)D;
+  // as ln_bwd_grp: the same trip count for every group of the wave (the shuffles span it), rows past M masked.  U
+  // rows per group and iteration: with the four partial rows and three parameter rows a lane holds here, two rows in
+  // flight (ln_bwd_grp's form) do not fit the registers that three waves per SIMD leave
+  constexpr int U = 1;
+  const long nrow_iter = (M + nslots - 1) / nslots;
+  for (long it = 0; it < nrow_iter; it += U) {
+    long row[U];
+    bool live[U];
+    float m1[U], r1[U], m2[U], r2[U], d[U][8], xh[U][8];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      row[u] = slot + (it + u) * nslots;
+      live[u] = act && row[u] < M;
+      m1[u] = row[u] < M ? mean1[row[u]] : 0.f;
+      r1[u] = row[u] < M ? rstd1[row[u]] : 0.f;
+      m2[u] = row[u] < M ? mean2[row[u]] : 0.f;
+      r2[u] = row[u] < M ? rstd2[row[u]] : 0.f;
+      if (live[u]) {
+        ldv<8>(dz + row[u] * D + c, d[u]);
+        ldv<8>(x + row[u] * D + c, xh[u]);
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        if (!live[u]) d[u][i] = xh[u][i] = 0.f;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      float o[8], yh[8], gz[8], s1 = 0.f, s2 = 0.f;
+      if (live[u] && dres) ldv<8>(dres + row[u] * D + c, o);   // (needed after the first reduction stage)
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        if (!live[u] || !dres) o[i] = 0.f;
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        xh[u][i] = live[u] ? (xh[u][i] - m1[u]) * r1[u] : 0.f;
+        yh[i] = live[u] ? (xh[u][i] * ga[i] + ba[i] - m2[u]) * r2[u] : 0.f;
+        gz[i] = d[u][i] * gb[i];
+        pg2[i] += d[u][i] * yh[i];
+        pb2[i] += d[u][i];
+        s1 += gz[i];
+        s2 += gz[i] * yh[i];
+      }
+      s1 = group_sum<G>(s1) * invd;
+      s2 = group_sum<G>(s2) * invd;
+      float t1 = 0.f, t2 = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        o[i] = live[u] ? o[i] + r2[u] * (gz[i] - s1 - yh[i] * s2) : 0.f;    // dy
+        gz[i] = o[i] * ga[i];                                                  // gy
+        pg1[i] += o[i] * xh[u][i];
+        pb1[i] += o[i];
+        t1 += gz[i];
+        t2 += gz[i] * xh[u][i];
+      }
+      t1 = group_sum<G>(t1) * invd;
+      t2 = group_sum<G>(t2) * invd;
+      if (live[u]) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] = r1[u] * (gz[i] - t1 - xh[u][i] * t2);
+        stv<8>(dx + row[u] * D + c, o);
+        if (dr.g2) {
+          float sc[8];
+          if (dr.p > 0.f) dropout_scale8(dr.p, dr.seed, (uint64_t)(row[u] * D + c), sc);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) sc[i] = dr.p > 0.f ? dr.scale * sc[i] : dr.scale;
+          float q[8];
+#pragma unroll
+          for (int i = 0; i < 8; ++i) q[i] = o[i] * sc[i];
+          st8_dyn(dr.g2, CFM_BF16, row[u] * D + c, q);
+        }
+      }
+    }
+  }
+  // fold the groups of the wave (they hold the same columns), then group 0 writes; one LDS block, both pairs in turn
+#pragma unroll
+  for (int o = G; o < 64; o <<= 1) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      pg1[i] += __shfl_xor(pg1[i], o, 64);
+      pb1[i] += __shfl_xor(pb1[i], o, 64);
+      pg2[i] += __shfl_xor(pg2[i], o, 64);
+      pb2[i] += __shfl_xor(pb2[i], o, 64);
+    }
+  }
+#pragma unroll
+  for (int blk = 0; blk < 2; ++blk) {
+    if (blk) __syncthreads();
+    if (lane < G) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        red[wv][c + i] = blk ? pg2[i] : pg1[i];
+        red[wv][8 * G + c + i] = blk ? pb2[i] : pb1[i];
+      }
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < 2 * D; q += 256) {
+      const int k = q < D ? q : 8 * G + (q - D);
+      ws[((long)blk * gridDim.x + blockIdx.x) * 2 * D + q] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
+    }
+  }
+}
+
 // ---------------------------------------------------------------- generic kernels (any D <= 1024)
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const void* __restrict__ x, int dtx,
                                                      const float* __restrict__ gamma,
@@ -682,6 +1060,16 @@ bool ln_bwd_grouped(const void* dy, int dtdy, const void* x, int dtx, const floa
   else go(std::integral_constant<int, 64>{});
   return true;
 }
+// which fused pair kernels serve width D with z / dz of dtype dtz: 0 none, 8 / 4 the one-row-per-wave kernels at that
+// V (D 512 / 256), -G the lane-group kernels.  D 128 and 1024 run ln_*_vec<2> / <16> in the two-call path and have no
+// fused form.  Pure host logic (cfm_layernorm_pair_ok).
+int ln_pair_kind(int D, int dtz) {
+  if (dtz != CFM_F32 && dtz != CFM_BF16) return 0;
+  if (D == 512) return 8;
+  if (D == 256) return 4;
+  if (D <= 0 || D == 128) return 0;
+  return -ln_group(D);
+}
 }  // namespace
 
 CFM_EXPORT int cfm_layernorm_fwd(const void* x, int dtx, const float* gamma, const float* beta, void* y, int dty,
@@ -805,4 +1193,107 @@ CFM_EXPORT int cfm_layernorm_bwd(const void* dy, int dtdy, const void* x, int dt
                                  void* stream) {
   return cfm_layernorm_bwd_drop(dy, dtdy, x, dtx, gamma, mean, rstd, dres, dtres, dx, dtdx, dgamma, dbeta, ws, M, D,
                                 nullptr, 0.f, 0.f, 0, stream);
+}
+
+CFM_EXPORT int cfm_layernorm_pair_ok(int D, int dtype_z) { return ln_pair_kind(D, dtype_z) != 0; }
+
+CFM_EXPORT size_t cfm_layernorm_fwd_pair_ws_bytes(long, int) { return 0; }
+
+CFM_EXPORT int cfm_layernorm_fwd_pair(const float* x, const float* gamma1, const float* beta1, const float* gamma2,
+                                      const float* beta2, float* y, void* z, int dtz, float* mean1, float* rstd1,
+                                      float* mean2, float* rstd2, long M, int D, float eps, void* stream) {
+  CFM_REQUIRE(x && gamma1 && beta1 && gamma2 && beta2 && y && z && mean1 && rstd1 && mean2 && rstd2, CFM_ERR_ARG,
+              "null pointer");
+  CFM_REQUIRE(M >= 0, CFM_ERR_SHAPE, "M >= 0");
+  const int kind = ln_pair_kind(D, dtz);
+  CFM_REQUIRE(kind != 0, CFM_ERR_SHAPE, "no fused pair kernel for this width / dtype (cfm_layernorm_pair_ok)");
+  CFM_REQUIRE(aligned16(x) && aligned16(y) && aligned16(z) && aligned16(gamma1) && aligned16(beta1) &&
+                  aligned16(gamma2) && aligned16(beta2),
+              CFM_ERR_ALIGN, "16-B aligned x / y / z / gamma / beta");
+  if (M == 0) return CFM_OK;
+  hipStream_t s = cfm::as_stream(stream);
+  auto vec = [&](auto vt) {
+    constexpr int V = decltype(vt)::value;
+    const dim3 g((unsigned)((M + 4 * LN_FWD_ROWS - 1) / (4 * LN_FWD_ROWS)));
+    if (dtz == CFM_BF16)
+      hipLaunchKernelGGL((ln_fwd_pair_vec<V, bf16>), g, dim3(256), 0, s, x, gamma1, beta1, gamma2, beta2, y, (bf16*)z,
+                         mean1, rstd1, mean2, rstd2, M, eps);
+    else
+      hipLaunchKernelGGL((ln_fwd_pair_vec<V, float>), g, dim3(256), 0, s, x, gamma1, beta1, gamma2, beta2, y,
+                         (float*)z, mean1, rstd1, mean2, rstd2, M, eps);
+  };
+  auto grp = [&](auto gt) {
+    constexpr int G = decltype(gt)::value;
+    const long rows_per_block = 4L * (64 / G) * LN_FWD_ROWS;
+    const dim3 g((unsigned)((M + rows_per_block - 1) / rows_per_block));
+    if (dtz == CFM_BF16)
+      hipLaunchKernelGGL((ln_fwd_pair_grp<G, bf16>), g, dim3(256), 0, s, x, gamma1, beta1, gamma2, beta2, y, (bf16*)z,
+                         mean1, rstd1, mean2, rstd2, M, D, eps);
+    else
+      hipLaunchKernelGGL((ln_fwd_pair_grp<G, float>), g, dim3(256), 0, s, x, gamma1, beta1, gamma2, beta2, y,
+                         (float*)z, mean1, rstd1, mean2, rstd2, M, D, eps);
+  };
+  if (kind == 8) vec(std::integral_constant<int, 8>{});
+  else if (kind == 4) vec(std::integral_constant<int, 4>{});
+  else if (kind == -16) grp(std::integral_constant<int, 16>{});
+  else if (kind == -32) grp(std::integral_constant<int, 32>{});
+  else grp(std::integral_constant<int, 64>{});
+  return cfm::check_launch("cfm_layernorm_fwd_pair");
+}
+
+CFM_EXPORT size_t cfm_layernorm_bwd_pair_ws_bytes(long M, int D) {
+  return (size_t)ln_bwd_blocks(M) * 4 * D * sizeof(float);
+}
+
+CFM_EXPORT int cfm_layernorm_bwd_pair(const void* dz, int dtdz, const float* dres, const float* x,
+                                      const float* gamma1, const float* beta1, const float* mean1, const float* rstd1,
+                                      const float* gamma2, const float* mean2, const float* rstd2, float* dx,
+                                      float* dgb1, float* dgb2, float* ws, long M, int D, void* g2, float g2_scale,
+                                      float g2_p, uint64_t g2_seed, void* stream) {
+  CFM_REQUIRE(dz && x && gamma1 && beta1 && mean1 && rstd1 && gamma2 && mean2 && rstd2 && dx && ws, CFM_ERR_ARG,
+              "null pointer");
+  CFM_REQUIRE(M >= 0, CFM_ERR_SHAPE, "M >= 0");
+  const int kind = ln_pair_kind(D, dtdz);
+  CFM_REQUIRE(kind != 0, CFM_ERR_SHAPE, "no fused pair kernel for this width / dtype (cfm_layernorm_pair_ok)");
+  CFM_REQUIRE(aligned16(dz) && aligned16(dres) && aligned16(x) && aligned16(dx) && aligned16(gamma1) &&
+                  aligned16(beta1) && aligned16(gamma2) && aligned16(g2),
+              CFM_ERR_ALIGN, "16-B aligned dz / dres / x / dx / gamma / beta / g2");
+  hipStream_t s = cfm::as_stream(stream);
+  const int nb = ln_bwd_blocks(M);
+  // g2 from the same pass where ln_bwd_* has it (V = 8 and the lane-group kernels); else a separate pass, as
+  // cfm_layernorm_bwd_drop
+  const bool g2_fused = g2 && kind != 4;
+  const LnDrop dr{g2_fused ? g2 : nullptr, g2_scale, g2_p, g2_seed, cfm::g_rng_salt};
+  auto vec = [&](auto vt) {
+    constexpr int V = decltype(vt)::value;
+    if (dtdz == CFM_BF16)
+      hipLaunchKernelGGL((ln_bwd_pair_vec<V, bf16>), dim3(nb), dim3(256), 0, s, (const bf16*)dz, dres, x, gamma1,
+                         beta1, mean1, rstd1, gamma2, mean2, rstd2, dx, ws, M, dr);
+    else
+      hipLaunchKernelGGL((ln_bwd_pair_vec<V, float>), dim3(nb), dim3(256), 0, s, (const float*)dz, dres, x, gamma1,
+                         beta1, mean1, rstd1, gamma2, mean2, rstd2, dx, ws, M, dr);
+  };
+  auto grp = [&](auto gt) {
+    constexpr int G = decltype(gt)::value;
+    if (dtdz == CFM_BF16)
+      hipLaunchKernelGGL((ln_bwd_pair_grp<G, bf16>), dim3(nb), dim3(256), 0, s, (const bf16*)dz, dres, x, gamma1,
+                         beta1, mean1, rstd1, gamma2, mean2, rstd2, dx, ws, M, D, dr);
+    else
+      hipLaunchKernelGGL((ln_bwd_pair_grp<G, float>), dim3(nb), dim3(256), 0, s, (const float*)dz, dres, x, gamma1,
+                         beta1, mean1, rstd1, gamma2, mean2, rstd2, dx, ws, M, D, dr);
+  };
+  if (kind == 8) vec(std::integral_constant<int, 8>{});
+  else if (kind == 4) vec(std::integral_constant<int, 4>{});
+  else if (kind == -16) grp(std::integral_constant<int, 16>{});
+  else if (kind == -32) grp(std::integral_constant<int, 32>{});
+  else grp(std::integral_constant<int, 64>{});
+  if (g2 && !g2_fused) {
+    const int rc = cfm_scale_dropout(dx, CFM_F32, g2, CFM_BF16, M * D, g2_scale, g2_p, g2_seed, 0, stream);
+    if (rc != CFM_OK) return rc;
+  }
+  float* part2 = ws + (long)nb * 2 * D;
+  if (dgb1 && dgb2) cfm::colreduce_pair(ws, part2, nb, 2L * D, dgb1, dgb2, s);
+  else if (dgb1) cfm::colreduce(ws, nb, 2L * D, dgb1, 0, s);
+  else if (dgb2) cfm::colreduce(part2, nb, 2L * D, dgb2, 0, s);
+  return cfm::check_launch("cfm_layernorm_bwd_pair");
 }

@@ -624,6 +624,61 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres=None, dx_dtype=torch.float32, s
     return dx, dgamma, dbeta
 
 
+def layernorm_pair_ok(D, dtype):
+    """True when the fused two-LayerNorm kernels (layernorm_fwd_pair / layernorm_bwd_pair) exist for width D with the
+    second output in `dtype` (cfm_layernorm_pair_ok: host logic, no GPU needed); else make the two calls."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        return False
+    return bool(L.load().cfm_layernorm_pair_ok(int(D), L.BF16 if dtype == torch.bfloat16 else L.F32))
+
+
+def layernorm_fwd_pair(x, gamma1, beta1, gamma2, beta2, eps=1e-5, out_dtype=None):
+    """y = LN(x; gamma1, beta1) (fp32) and z = LN(y; gamma2, beta2) (out_dtype) from one kernel, bit-identical to two
+    layernorm_fwd calls -> (y, z, mean1, rstd1, mean2, rstd2)."""
+    M, D = x.shape
+    y = torch.empty(M, D, device=x.device, dtype=torch.float32)
+    z = torch.empty(M, D, device=x.device, dtype=out_dtype or torch.float32)
+    st = torch.empty(4, M, device=x.device, dtype=torch.float32)
+    L.call("cfm_layernorm_fwd_pair", L.ptr(x), L.ptr(gamma1), L.ptr(beta1), L.ptr(gamma2), L.ptr(beta2), L.ptr(y),
+           L.ptr(z), L.dt(z), L.ptr(st[0]), L.ptr(st[1]), L.ptr(st[2]), L.ptr(st[3]), M, D, float(eps), L.stream())
+    return y, z, st[0], st[1], st[2], st[3]
+
+
+def layernorm_bwd_pair(dz, dres, x, gamma1, beta1, mean1, rstd1, gamma2, mean2, rstd2, side=None, drop=None):
+    """Backward of layernorm_fwd_pair: dz the gradient of z, dres (fp32 or None) the gradient reaching y directly.
+    -> (dx, (dgamma1, dbeta1), (dgamma2, dbeta2), g2); side / drop as layernorm_bwd (g2 is None without drop)."""
+    M, D = x.shape
+    dx = torch.empty(M, D, device=x.device, dtype=torch.float32)
+    gb1 = torch.empty(2, D, device=x.device, dtype=torch.float32)
+    gb2 = torch.empty(2, D, device=x.device, dtype=torch.float32)
+    nbytes = L.size_call("cfm_layernorm_bwd_pair_ws_bytes", M, D)
+    ws = workspace(nbytes, x.device)
+    defer = side is not None
+    g2 = None
+    fused_g2 = drop is not None and drop[3] == torch.bfloat16
+    scale, p, seed = (float(drop[0]), float(drop[1]), int(drop[2])) if fused_g2 else (0.0, 0.0, 0)
+    if fused_g2:
+        g2 = torch.empty(M, D, device=x.device, dtype=torch.bfloat16)
+    L.call("cfm_layernorm_bwd_pair", L.ptr(dz), L.dt(dz), L.ptr(dres), L.ptr(x), L.ptr(gamma1), L.ptr(beta1),
+           L.ptr(mean1), L.ptr(rstd1), L.ptr(gamma2), L.ptr(mean2), L.ptr(rstd2), L.ptr(dx),
+           None if defer else L.ptr(gb1), None if defer else L.ptr(gb2), L.ptr(ws), M, D, L.ptr(g2), scale, p, seed,
+           L.stream())
+    if drop is not None and not fused_g2:
+        g2 = scale_dropout(dx, drop[0], drop[1], drop[2], 0, out_dtype=drop[3])
+    if defer:
+        nb = nbytes // (16 * D)
+        parts = (ws, ws[nb * 2 * D:])
+        if getattr(side, "rgroup", None) is not None:      # two tasks of the grouped reduction at the end of backward
+            for part, gb in zip(parts, (gb1, gb2)):
+                side.rgroup.add_sum(part, nb, 2 * D, 2 * D, gb)
+        else:
+            def reduce():
+                for part, gb in zip(parts, (gb1, gb2)):
+                    L.call("cfm_colreduce", L.ptr(part), nb, 2 * D, 2 * D, L.ptr(gb), 0, L.stream())
+            side.run(reduce, ws, gb1, gb2)
+    return dx, (gb1[0], gb1[1]), (gb2[0], gb2[1]), g2
+
+
 def scale_dropout(x, scale=1.0, drop_p=0.0, seed=0, offset=0, out_dtype=None):
     y = torch.empty(x.shape, device=x.device, dtype=out_dtype or x.dtype)
     L.call("cfm_scale_dropout", L.ptr(x), L.dt(x), L.ptr(y), L.dt(y), x.numel(), float(scale), float(drop_p),
