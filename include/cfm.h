@@ -477,6 +477,37 @@ int cfm_glu_dwconv_bwd_bn(const void* dz, int dtype_dz, const float* y, const fl
                           const float* mean, const float* invstd, const float* dbeta, const float* dgamma,
                           float invM, int training, const void* a, int dtype_a, const float* w_dw, void* da,
                           int dtype_da, float* dw, float* db, int B, int T, int C, int K, float* ws, void* stream);
+/* use_group_norm=True: torch.nn.GroupNorm(1, C, eps, affine) in place of the BatchNorm1d (torchaudio
+ * _ConvolutionModule; oracle/conformer.py ConvModuleRef).  Statistics are per sample b over ALL T*C elements of
+ * that sample, padded frames included (nothing is masked, as for BatchNorm), variance biased, no running
+ * statistics, train == eval.  One-pass (sum, sumsq) statistics like the BatchNorm path: finalised in double from
+ * the [2][nparts][C] partials cfm_glu_dwconv_fwd left in ws (rows b*ceil(T/64) .. of sample b), fixed summation
+ * order, no atomics.
+ *   fwd:  z = silu((y - mean[b]) * rstd[b] * gamma[c] + beta[c]);  mean, rstd: (B) fp32, saved for the backward.
+ *   bwd:  yhat = (y - mean[b]) * rstd[b],  du = dz * silu'(yhat*gamma[c] + beta[c]),
+ *         dbeta[c] = sum_{b,t} du,  dgamma[c] = sum_{b,t} du*yhat,
+ *         k1[b] = (1/(T*C)) sum_{t,c} gamma[c]*du,  k2[b] = (1/(T*C)) sum_{t,c} gamma[c]*du*yhat,
+ *         dy = rstd[b] * (gamma[c]*du - k1[b] - yhat*k2[b]).
+ * coef: caller-provided (B, 2) fp32 buffer of (k1[b], k2[b]) rows -- NOT part of ws, because the depthwise
+ * backward that reads it overwrites ws with its weight-gradient partials. */
+int cfm_gn_silu_fwd(const float* y, const float* gamma, const float* beta, float eps, float* mean, float* rstd,
+                    void* z, int dtype_z, int B, int T, int C, const float* ws, void* stream);
+/* one pass over dz and y: dbeta, dgamma (C each, =) and coef (B, 2); ws: cfm_convmod_ws_bytes (used for the
+ * [2][nparts][C] partials of (sum du, sum du*yhat)). */
+int cfm_gn_silu_bwd_sums(const void* dz, int dtype_dz, const float* y, const float* gamma, const float* beta,
+                         const float* mean, const float* rstd, int B, int T, int C, float* ws, float* dbeta,
+                         float* dgamma, float* coef, void* stream);
+/* cfm_glu_dwconv_bwd with dy formed inside the depthwise kernel from dz, y, the statistics and coef (after
+ * cfm_gn_silu_bwd_sums), never stored.  K must be one of 3, 5, 7, 15, 31, 33.  dw == NULL: partials left in ws
+ * for cfm_glu_dwconv_bwd_wgrad. */
+int cfm_glu_dwconv_bwd_gn(const void* dz, int dtype_dz, const float* y, const float* gamma, const float* beta,
+                          const float* mean, const float* rstd, const float* coef, const void* a, int dtype_a,
+                          const float* w_dw, void* da, int dtype_da, float* dw, float* db, int B, int T, int C, int K,
+                          float* ws, void* stream);
+/* unfused fallback (any K): the sums above, then dy (B*T, C) fp32 written; cfm_glu_dwconv_bwd follows it. */
+int cfm_gn_silu_bwd(const void* dz, int dtype_dz, const float* y, const float* gamma, const float* beta,
+                    const float* mean, const float* rstd, float* dy, float* dgamma, float* dbeta, float* coef,
+                    int B, int T, int C, float* ws, void* stream);
 
 /* ---------------------------------------------------------------- Attention
  * nn.MultiheadAttention(need_weights=False, key_padding_mask) core (torchaudio ConformerLayer

@@ -199,6 +199,11 @@ _SIGS = {
     "cfm_glu_dwconv_bwd_bn": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_float, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                       c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cfm_gn_silu_fwd": (c_int, [c_void_p] * 3 + [c_float] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 2),
+    "cfm_gn_silu_bwd_sums": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int] * 3 + [c_void_p] * 5),
+    "cfm_gn_silu_bwd": (c_int, [c_void_p, c_int] + [c_void_p] * 9 + [c_int] * 3 + [c_void_p] * 2),
+    "cfm_glu_dwconv_bwd_gn": (c_int, [c_void_p, c_int] + [c_void_p] * 7 + [c_int, c_void_p, c_void_p, c_int,
+                                      c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "cfm_glu_dwconv_bwd_wgrad": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "cfm_glu_dwconv_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                    c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -127,7 +127,8 @@ LN_PAIR = os.environ.get("CFM_LN_PAIR", "1") != "0"
 class _Cfg:
     __slots__ = ("B", "T", "d", "H", "ffn", "K", "p", "cd", "training", "conv_first", "rel", "seed",
                  "bn_rm", "bn_rv", "bn_mom", "pe", "shadow", "shadow_t", "group_wgrad", "layer_index",
-                 "grad_dest", "flush_here", "on_flushed", "on_routed", "sync_bn", "shadow8", "pos_pre", "rdt", "rfuse")
+                 "grad_dest", "flush_here", "on_flushed", "on_routed", "sync_bn", "shadow8", "pos_pre", "rdt", "rfuse",
+                 "gn", "gn_eps")
 
 
 # the 2-D (and pointwise-conv) weight matrices of _PNAMES: cast to the compute dtype once per step
@@ -395,7 +396,9 @@ def _conv_fwd(x, P, cfg, seed, dprev=None):
     a = ops.linear(xn, wp1, P[15])
     ws = ops.convmod_ws(B, T, d, K, x.device)
     yv = ops.glu_dwconv_fwd(a, wdw, P[17], B, T, d, K, ws)
-    if cfg.sync_bn is not None and cfg.training:
+    if cfg.gn:      # GroupNorm(1, d): per-utterance statistics (B,), the same function in train and eval
+        z, bmean, binv = ops.gn_silu_fwd(yv, P[18], P[19], cfg.gn_eps, B, T, d, ws, cd)
+    elif cfg.sync_bn is not None and cfg.training:
         z, bmean, binv = ops.bn_silu_fwd_sync(yv, P[18], P[19], cfg.bn_rm, cfg.bn_rv, cfg.bn_mom, _EPS, B, T, d, ws,
                                               cd, cfg.sync_bn[0], cfg.sync_bn[1])
     else:
@@ -417,7 +420,14 @@ def _conv_bwd(g, x, sv, P, cfg, seed, grads, side, g2=None, nxt=None):
     ws = ops.convmod_ws(B, T, d, K, x.device)
     sync = cfg.sync_bn is not None and cfg.training
     dy = None
-    if K in ops.BN_FOLD_K and "bnfold" not in ops.DISABLED:     # (CFM_DISABLE=bnfold: separate BN backward, A/B)
+    fold = K in ops.BN_FOLD_K and "bnfold" not in ops.DISABLED  # (CFM_DISABLE=bnfold: separate norm backward, A/B)
+    if cfg.gn and fold:
+        da, dwdw, grads[17], grads[18], grads[19] = ops.gn_silu_glu_dwconv_bwd(
+            dz, yv, P[18], P[19], bmean, binv, a, wdw, B, T, d, K, ws, cd, side=side)
+    elif cfg.gn:
+        dy, grads[18], grads[19] = ops.gn_silu_bwd(dz, yv, P[18], P[19], bmean, binv, B, T, ws)
+        da, dwdw, grads[17] = ops.glu_dwconv_bwd(dy, a, wdw, B, T, d, K, ws, cd, side=side)
+    elif fold:
         da, dwdw, grads[17], grads[18], grads[19] = ops.bn_silu_glu_dwconv_bwd(
             dz, yv, P[18], P[19], bmean, binv, cfg.training, a, wdw, B, T, d, K, ws, cd, side=side,
             reduce_sums=cfg.sync_bn[0] if sync else None, world=cfg.sync_bn[1] if sync else 1)
@@ -576,8 +586,6 @@ class ConformerLayer(nn.Module):
     def __init__(self, input_dim, ffn_dim, num_attention_heads, depthwise_conv_kernel_size, dropout=0.0,
                  use_group_norm=False, convolution_first=False, pos_enc="none"):
         super().__init__()
-        if use_group_norm:
-            raise NotImplementedError("use_group_norm=True: GroupNorm conv module is not on the MI355X path yet")
         self.ffn1 = _FFNParams(input_dim, ffn_dim, dropout)
         self.self_attn_layer_norm = nn.LayerNorm(input_dim)
         self.self_attn = _MHAParams(input_dim, num_attention_heads, dropout, pos_enc)
@@ -586,6 +594,7 @@ class ConformerLayer(nn.Module):
         self.ffn2 = _FFNParams(input_dim, ffn_dim, dropout)
         self.final_layer_norm = nn.LayerNorm(input_dim)
         self.convolution_first = convolution_first
+        self.use_group_norm = bool(use_group_norm)
         self.dropout = dropout
         self.pos_enc = pos_enc
         self.d, self.H, self.ffn, self.K = input_dim, num_attention_heads, ffn_dim, depthwise_conv_kernel_size
@@ -617,15 +626,21 @@ class ConformerLayer(nn.Module):
         cfg.rel = self.pos_enc == "rel"
         cfg.seed = seed
         bn = self.conv_module.sequential[3]
-        cfg.bn_rm, cfg.bn_rv = bn.running_mean, bn.running_var
-        cfg.bn_mom = bn.momentum if bn.momentum is not None else 0.1
+        cfg.gn = self.use_group_norm
+        if cfg.gn:      # GroupNorm(1, d): no running statistics, no momentum, no batch counter
+            cfg.bn_rm = cfg.bn_rv = None
+            cfg.bn_mom = 0.0
+            cfg.gn_eps = bn.eps
+        else:
+            cfg.bn_rm, cfg.bn_rv = bn.running_mean, bn.running_var
+            cfg.bn_mom = bn.momentum if bn.momentum is not None else 0.1
         cfg.pe = pe
         cfg.pos_pre = pos_pre
         cfg.layer_index = layer_index
         cfg.group_wgrad = bool(group_wgrad) and "wgroup" not in ops.DISABLED
         cfg.grad_dest, cfg.flush_here, cfg.on_flushed, cfg.on_routed = grad_dest, flush_here, on_flushed, on_routed
         cfg.sync_bn = sync_bn
-        if count_batches and self.training and bn.track_running_stats:
+        if count_batches and self.training and not cfg.gn and bn.track_running_stats:
             bn.num_batches_tracked.add_(1)
         ng, nb = next_ln if next_ln is not None else (None, None)
         return _ConformerLayerFn.apply(x, lens_i32, cfg, xn_in, ng, nb, *self.params())
@@ -757,7 +772,9 @@ class Conformer(nn.Module):
         """torch.nn.SyncBatchNorm semantics for every ConvModule BatchNorm (train mode): batch statistics and
         the input-gradient sums over all replicas of `group` (default: the default process group), one
         all-reduce of 2*d floats per BN per pass; each rank's weight/bias gradients stay local (the data-
-        parallel gradient all-reduce averages them).  group=False turns it off."""
+        parallel gradient all-reduce averages them).  group=False turns it off.
+        GroupNorm layers (use_group_norm=True) are left alone: their statistics are per utterance, so they are
+        already the same on every replica and need no all-reduce."""
         import torch.distributed as dist
         if group is False or not (dist.is_available() and dist.is_initialized()):
             self.sync_bn = None
@@ -805,9 +822,10 @@ class Conformer(nn.Module):
                                      pos_pre=None if pos_all is None else pos_all[i], xn_in=xn,
                                      next_ln=None if nxt is None else (nxt.weight, nxt.bias))
             x, xn = x if nxt is not None else (x, None)
-        # every layer's BatchNorm num_batches_tracked += 1 in one multi-tensor launch (not one per layer)
-        counters = [ly.conv_module.sequential[3].num_batches_tracked for ly in self.conformer_layers
-                    if self.training and ly.conv_module.sequential[3].track_running_stats]
+        # every layer's BatchNorm num_batches_tracked += 1 in one multi-tensor launch (not one per layer); GroupNorm
+        # layers have no counter
+        norms = [ly.conv_module.sequential[3] for ly in self.conformer_layers if not ly.use_group_norm]
+        counters = [bn.num_batches_tracked for bn in norms if self.training and bn.track_running_stats]
         if counters:
             torch._foreach_add_(counters, 1)
         return x
@@ -832,7 +850,7 @@ class Conformer(nn.Module):
             x = library.layer_forward(layer, x, lens_i32, B, T, self.compute_dtype, base + 100 * i)
         for ly in self.conformer_layers:
             bn = ly.conv_module.sequential[3]
-            if self.training and bn.track_running_stats:
+            if self.training and not ly.use_group_norm and bn.track_running_stats:
                 bn.num_batches_tracked.add_(1)
         return x
 

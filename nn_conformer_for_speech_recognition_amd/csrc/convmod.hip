@@ -1,5 +1,5 @@
 // convmod.hip — the HBM-bound middle of torchaudio's _ConvolutionModule:
-//   GLU(dim=channel) -> depthwise Conv1d(K, 'same' zero padding, bias) -> BatchNorm1d -> SiLU
+//   GLU(dim=channel) -> depthwise Conv1d(K, 'same' zero padding, bias) -> BatchNorm1d | GroupNorm(1, C) -> SiLU
 // and its backward, plus the generic BatchNorm1d of the projection block.
 // Token-major layout (row = b*T + t, channel contiguous) so every load is coalesced across
 // channels; each workgroup owns a 64-channel x TT-frame tile of one utterance and stages the GLU
@@ -402,22 +402,182 @@ __global__ void bn_bwd_apply_total_kernel(const void* __restrict__ dz, int dtdz,
   }
 }
 
+// ----------------------------------------------------------------------------- GroupNorm(1, C) (use_group_norm)
+// torch.nn.GroupNorm(num_groups=1) between the depthwise conv and SiLU: one (mean, rstd) per utterance over all
+// T*C elements of that utterance, padded frames included (torchaudio masks nothing here), biased variance, no
+// running statistics.  One-pass (sum, sumsq) statistics from the depthwise forward's partials, as for BatchNorm.
+
+// Sample b's two reductions over its nt partial rows x C columns, one workgroup (16 waves) per sample:
+//   COEF = false: (sum, sumsq) of y      -> o0[b] = mean, o1[b] = rstd
+//   COEF = true : gamma-weighted (P1, P2) -> o0[2b] = k1, o0[2b+1] = k2   (the backward's per-sample coefficients)
+// Rows b*nt .. b*nt+nt-1 of a [nparts][C] array are contiguous, so the threads walk one flat range.  Fixed order,
+// no atomics: each thread adds its strided elements in double, a wave adds by xor-shuffle, thread 0 adds the 16
+// wave sums in order and finalises in double.
+template <bool COEF>
+__global__ __launch_bounds__(1024) void gn_sample_kernel(const float* __restrict__ partA,
+                                                         const float* __restrict__ partB, int nt, int C,
+                                                         const float* __restrict__ gamma, double invN, float eps,
+                                                         float* __restrict__ o0, float* __restrict__ o1) {
+  __shared__ double red[2][16];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long base = (long)b * nt * C;
+  const int n = nt * C;
+  double sa = 0.0, sb = 0.0;
+  // 8 strided elements of both arrays in flight per thread (clamped addresses, zeroed after the fact): one element
+  // per iteration paid a memory round trip each, 12 in a row at T 1498
+  for (int i0 = threadIdx.x; i0 < n; i0 += 1024 * 8) {
+    float va[8], vb[8], vg[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int i = min(i0 + 1024 * u, n - 1);
+      va[u] = partA[base + i];
+      vb[u] = partB[base + i];
+      if constexpr (COEF) vg[u] = gamma[i % C];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const bool ok = i0 + 1024 * u < n;
+      float xa = ok ? va[u] : 0.f, xb = ok ? vb[u] : 0.f;
+      if constexpr (COEF) {
+        xa *= vg[u];
+        xb *= vg[u];
+      }
+      sa += (double)xa;
+      sb += (double)xb;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    sa += __shfl_xor(sa, o, 64);
+    sb += __shfl_xor(sb, o, 64);
+  }
+  if (lane == 0) {
+    red[0][wv] = sa;
+    red[1][wv] = sb;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    s1 += red[0][q];
+    s2 += red[1][q];
+  }
+  if constexpr (COEF) {
+    o0[2 * b] = (float)(s1 * invN);
+    o0[2 * b + 1] = (float)(s2 * invN);
+  } else {
+    const double mu = s1 * invN;
+    double var = s2 * invN - mu * mu;
+    if (var < 0.0) var = 0.0;
+    o0[b] = (float)mu;
+    o1[b] = (float)(1.0 / sqrt(var + (double)eps));
+  }
+}
+
+// z = silu((y - mean[b]) * rstd[b] * gamma[c] + beta[c]);  any C, any dtype_z
+__global__ void gn_apply_kernel(const float* __restrict__ y, const float* __restrict__ gamma,
+                                const float* __restrict__ beta, const float* __restrict__ mean,
+                                const float* __restrict__ rstd, void* __restrict__ z, int dtz, int B, int T, int C) {
+  const long tc = (long)T * C, n = tc * B;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C), b = (int)(i / tc);
+    st_dyn(z, dtz, i, silu_f((y[i] - mean[b]) * rstd[b] * gamma[c] + beta[c]));
+  }
+}
+
+// 8 consecutive elements per thread, one pass (C % 8 == 0, 16-B aligned), as bn_apply_vec8: the 8 elements share a
+// row, hence a sample
+template <int DTZ>
+__global__ __launch_bounds__(256) void gn_apply_vec8(const float* __restrict__ y, const float* __restrict__ gamma,
+                                                     const float* __restrict__ beta, const float* __restrict__ mean,
+                                                     const float* __restrict__ rstd, void* __restrict__ z, int B,
+                                                     int T, int C) {
+  const long tc = (long)T * C;
+  const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 8;
+  if (i >= tc * B) return;
+  const int c = (int)(i % C), b = (int)(i / tc);
+  const float mu = mean[b], rs = rstd[b];
+  float v[8];
+  ld8_dyn(y, CFM_F32, i, v);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = silu_f((v[e] - mu) * rs * gamma[c + e] + beta[c + e]);
+  st8_dyn(z, DTZ, i, v);
+}
+
+// [2][nparts][C] partials of (sum du, sum du*yhat) on the depthwise grid (ceil(C/CT), ceil(T/TT), B), part index
+// b*gridDim.y + blockIdx.y as in the forward; lane = channel, wave w takes frames w, w+4, ...
+//   du = dz * silu'(yhat*gamma + beta),  yhat = (y - mean[b]) * rstd[b]
+__global__ __launch_bounds__(256) void gn_bwd_sums_kernel(const void* __restrict__ dz, int dtdz,
+                                                          const float* __restrict__ y,
+                                                          const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta,
+                                                          const float* __restrict__ mean,
+                                                          const float* __restrict__ rstd, int T, int C,
+                                                          float* __restrict__ part) {
+  __shared__ float red[2][4][CT];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int c = blockIdx.x * CT + lane;
+  const int t0 = blockIdx.y * TT, b = blockIdx.z;
+  const int t1 = min(T, t0 + TT);
+  float sd = 0.f, sdx = 0.f;
+  if (c < C) {
+    const float mu = mean[b], rs = rstd[b], g = gamma[c], bt = beta[c];
+    for (int t = t0 + wv; t < t1; t += 4) {
+      const long i = ((long)b * T + t) * C + c;
+      const float yh = (y[i] - mu) * rs;
+      const float du = ld_dyn(dz, dtdz, i) * silu_grad_f(yh * g + bt);
+      sd += du;
+      sdx += du * yh;
+    }
+  }
+  red[0][wv][lane] = sd;
+  red[1][wv][lane] = sdx;
+  __syncthreads();
+  if (wv == 0 && c < C) {
+    const long part_idx = (long)b * gridDim.y + blockIdx.y;
+    const long nparts = (long)gridDim.z * gridDim.y;
+    part[part_idx * C + c] = red[0][0][lane] + red[0][1][lane] + red[0][2][lane] + red[0][3][lane];
+    part[(nparts + part_idx) * C + c] = red[1][0][lane] + red[1][1][lane] + red[1][2][lane] + red[1][3][lane];
+  }
+}
+
+// dy = rstd[b] * (gamma[c]*du - k1[b] - yhat*k2[b])  (unfused fallback: kernel sizes without a compiled variant)
+__global__ void gn_bwd_apply_kernel(const void* __restrict__ dz, int dtdz, const float* __restrict__ y,
+                                    const float* __restrict__ gamma, const float* __restrict__ beta,
+                                    const float* __restrict__ mean, const float* __restrict__ rstd,
+                                    const float* __restrict__ coef, float* __restrict__ dy, int B, int T, int C) {
+  const long tc = (long)T * C, n = tc * B;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C), b = (int)(i / tc);
+    const float rs = rstd[b], g = gamma[c];
+    const float yh = (y[i] - mean[b]) * rs;
+    const float du = ld_dyn(dz, dtdz, i) * silu_grad_f(yh * g + beta[c]);
+    dy[i] = rs * (g * du - coef[2 * b] - yh * coef[2 * b + 1]);
+  }
+}
+
 // BatchNorm1d + SiLU backward folded into the depthwise-conv backward (BN=true): the kernel reads dz (the
 // pointwise-conv-2 data gradient) and the BN input y and forms the BN input gradient
 //   dy = gamma * invstd * (du - dbeta / M - yhat * dgamma / M)   (train; eval: gamma * invstd * du)
 //   du = dz * silu'(yhat * gamma + beta),  yhat = (y - mean) * invstd
 // on the fly, so the fp32 dy never goes through HBM (one write + one read of B*T*C floats and a launch saved).
+// GN=true folds the GroupNorm(1, C) + SiLU backward the same way: mean / invstd are per sample (B each), coef is the
+// (B, 2) buffer of (k1, k2) from cfm_gn_silu_bwd_sums, and
+//   dy = rstd[b] * (gamma[c] * du - k1[b] - yhat * k2[b]),  yhat = (y - mean[b]) * rstd[b]
+// (dgamma, dbeta, invM and training are not read).
 struct BnBwd {
   const void* dz; int dtdz;
   const float* y;
   const float *gamma, *beta, *mean, *invstd, *dgamma, *dbeta;
   float invM;
   int training;
+  const float* coef;
 };
 
 // backward of y = dwconv(GLU(a)).  grid (ceil(C/CT), ceil(T/TT), B)
 // part: [nparts][K+1][C] per-block partial dw (K taps) and db (tap K).
-template <int KT, typename TA, bool BN = false>
+template <int KT, typename TA, bool BN = false, bool GN = false>
 __global__ __launch_bounds__(256) void glu_dwconv_bwd_kernel(const float* __restrict__ dy,
                                                              const void* __restrict__ a, int dta,
                                                              const float* __restrict__ w, void* __restrict__ da,
@@ -443,6 +603,11 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_kernel(const float* __rest
       bk1 = bn.training ? bn.dbeta[cc] * bn.invM : 0.f;
       bk2 = bn.training ? bn.dgamma[cc] * bn.invM : 0.f;
     }
+    if constexpr (GN) {
+      bg = bn.gamma[cc]; bis = bn.invstd[b]; bmu = bn.mean[b]; bbt = bn.beta[cc];
+      bk1 = bn.coef[2 * b];
+      bk2 = bn.coef[2 * b + 1];
+    }
 #pragma unroll
     for (int i = 0; i < NR; ++i) {
       const int t = min(max(t0 - pad + wv + 4 * i, 0), T - 1);
@@ -451,6 +616,10 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_kernel(const float* __rest
         const float yh = (bn.y[row * C + cc] - bmu) * bis;
         const float du = ld_dyn(bn.dz, bn.dtdz, row * C + cc) * silu_grad_f(yh * bg + bbt);
         dv[i] = bg * bis * (du - bk1 - yh * bk2);
+      } else if constexpr (GN) {
+        const float yh = (bn.y[row * C + cc] - bmu) * bis;
+        const float du = ld_dyn(bn.dz, bn.dtdz, row * C + cc) * silu_grad_f(yh * bg + bbt);
+        dv[i] = bis * (bg * du - bk1 - yh * bk2);
       } else {
         dv[i] = dy[row * C + cc];
       }
@@ -467,7 +636,7 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_kernel(const float* __rest
       }
     }
   } else {
-    static_assert(!BN || KT > 0, "BN folding: compiled kernel sizes only");
+    static_assert(!(BN || GN) || KT > 0, "BN / GN folding: compiled kernel sizes only");
     for (int r = wv; r < rows; r += 4) {
       const int t = t0 - pad + r;
       float vd = 0.f, vg = 0.f;
@@ -585,11 +754,13 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_kernel(const float* __rest
 // depthwise math stays lane = channel out of LDS.  The GLU-input gradient goes back through LDS so the lane that
 // staged a row's GLU inputs also writes that row's da from its registers (no second read of a).
 // Staging map: thread = (row group rs = tid / 16, channel quad q = tid % 16); pass p covers rows rs + 16 p.
-template <int KT, bool BN, bool DZ16>
+template <int KT, bool BN, bool DZ16, bool GN = false>
 __global__ __launch_bounds__(256) void glu_dwconv_bwd_vec_kernel(const float* __restrict__ dy,
                                                                  const bf16* __restrict__ a,
                                                                  const float* __restrict__ w, bf16* __restrict__ da,
                                                                  int T, int C, float* __restrict__ part, BnBwd bn) {
+  static_assert(!(BN && GN), "one norm at a time");
+  constexpr bool NORM = BN || GN;    // the staging reads y and dz instead of dy
   constexpr int PAD = (KT - 1) / 2, ROWS = TT + KT - 1, NP = (ROWS + 15) / 16;
   constexpr int FB = TT / 4, WN = FB + KT - 1;
   constexpr int L_STAGE = 2 * ROWS * CT, L_OUT = TT * CT + 4 * (KT + 1) * CT;
@@ -620,6 +791,16 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_vec_kernel(const float* __
       bk2 = bk1;
     }
   }
+  // GN: the sample's rstd, -mean * rstd, -rstd * k1, -rstd * k2 (wave-uniform)
+  float gis = 0.f, gnm = 0.f, gk1 = 0.f, gk2 = 0.f;
+  if constexpr (GN) {
+    bg = *reinterpret_cast<const f32x4*>(bn.gamma + cqc);
+    bbt = *reinterpret_cast<const f32x4*>(bn.beta + cqc);
+    gis = bn.invstd[b];
+    gnm = -bn.mean[b] * gis;
+    gk1 = -gis * bn.coef[2 * b];
+    gk2 = -gis * bn.coef[2 * b + 1];
+  }
   f32x4 v4[NP];
   bf16x4 z4[NP];
   bf16x4 x4[NP], g4[NP];
@@ -627,7 +808,7 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_vec_kernel(const float* __
   for (int p = 0; p < NP; ++p) {
     const int t = min(max(t0 - PAD + rs + 16 * p, 0), T - 1);
     const long row = (long)b * T + t;
-    if constexpr (BN) {
+    if constexpr (NORM) {
       v4[p] = *reinterpret_cast<const f32x4*>(bn.y + row * C + cqc);
       if constexpr (DZ16) z4[p] = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16*>(bn.dz) + row * C + cqc);
     } else {
@@ -637,7 +818,7 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_vec_kernel(const float* __
     g4[p] = *reinterpret_cast<const bf16x4*>(a + row * 2 * C + C + cqc);
   }
   f32x4 zf[NP];
-  if constexpr (BN && !DZ16) {
+  if constexpr (NORM && !DZ16) {
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
       const int t = min(max(t0 - PAD + rs + 16 * p, 0), T - 1);
@@ -658,6 +839,13 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_vec_kernel(const float* __
       bbt2[h2] = f2{bbt[2 * h2], bbt[2 * h2 + 1]};
       bk1_2[h2] = f2{bk1[2 * h2], bk1[2 * h2 + 1]};
       bk2_2[h2] = f2{bk2[2 * h2], bk2[2 * h2 + 1]};
+    }
+  }
+  if constexpr (GN) {   // gi2 = gamma * rstd; bbt2 = beta - mean * rstd * gamma, so yhat * gamma + beta = y * gi2 + bbt2
+#pragma unroll
+    for (int h2 = 0; h2 < 2; ++h2) {
+      gi2[h2] = f2{bg[2 * h2] * gis, bg[2 * h2 + 1] * gis};
+      bbt2[h2] = f2{fmaf(gnm, bg[2 * h2], bbt[2 * h2]), fmaf(gnm, bg[2 * h2 + 1], bbt[2 * h2 + 1])};
     }
   }
   f32x4 sg4[NP];
@@ -682,6 +870,17 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_vec_kernel(const float* __
           else dz = f2{zf[p][2 * h2], zf[p][2 * h2 + 1]};
           const f2 du = dz * sgr;
           dv = gi2[h2] * (__builtin_elementwise_fma(-yh, bk2_2[h2], du) - bk1_2[h2]);
+        } else if constexpr (GN) {
+          const f2 v = {v4[p][2 * h2], v4[p][2 * h2 + 1]};
+          const f2 yh = __builtin_elementwise_fma(v, f2{gis, gis}, f2{gnm, gnm});
+          const f2 pre = __builtin_elementwise_fma(v, gi2[h2], bbt2[h2]);     // yhat * gamma + beta
+          const f2 sgm = {sigmoid_f(pre.x), sigmoid_f(pre.y)};
+          const f2 sgr = __builtin_elementwise_fma(sgm, pre * (f2{1.f, 1.f} - sgm), sgm);
+          f2 dz;
+          if constexpr (DZ16) dz = f2{(float)z4[p][2 * h2], (float)z4[p][2 * h2 + 1]};
+          else dz = f2{zf[p][2 * h2], zf[p][2 * h2 + 1]};
+          // rstd * (gamma * du - k1 - yhat * k2)
+          dv = __builtin_elementwise_fma(gi2[h2], dz * sgr, __builtin_elementwise_fma(yh, f2{gk2, gk2}, f2{gk1, gk1}));
         } else {
           dv = f2{v4[p][2 * h2], v4[p][2 * h2 + 1]};
         }
@@ -835,7 +1034,7 @@ bool g_dwconv_scalar = getenv("CFM_DWCONV_SCALAR") != nullptr;   // A/B: the one
 
 CFM_EXPORT size_t cfm_convmod_ws_bytes(int B, int T, int C, int K) {
   const long np = conv_nparts(B, T);
-  const long fwd = 2 * np * C + 2L * C;
+  const long fwd = 2 * np * C + 2L * C;   // also the GroupNorm backward's [2][nparts][C] (sum du, sum du*yhat) partials
   const long bwd = np * (long)C * (K + 1) + (long)C * (K + 1);
   const long bn = 2L * BN_PARTS * C;
   long m = fwd > bwd ? fwd : bwd;
@@ -941,15 +1140,17 @@ namespace {
 
 // the vectorised backward for bf16 a/da, C % 4 == 0 and a compiled K; false if not eligible
 bool dwconv_bwd_vec(const float* dy, const void* a, int dta, const float* w, void* da, int dtda, int B, int T, int C,
-                    int K, float* ws, const BnBwd& bn, bool use_bn, hipStream_t s) {
+                    int K, float* ws, const BnBwd& bn, bool use_bn, hipStream_t s, bool use_gn = false) {
   if (g_dwconv_scalar || dta != CFM_BF16 || dtda != CFM_BF16 || (C % 4) != 0) return false;
-  const bool dz16 = use_bn && bn.dtdz == CFM_BF16;
+  const bool dz16 = (use_bn || use_gn) && bn.dtdz == CFM_BF16;
   dim3 grid(cdiv(C, CT), cdiv(T, TT), B);
   const bf16* ab = reinterpret_cast<const bf16*>(a);
   bf16* dab = reinterpret_cast<bf16*>(da);
   switch (K) {
 #define X(k) case k:                                                                                             \
-    if (!use_bn) hipLaunchKernelGGL((glu_dwconv_bwd_vec_kernel<k, false, false>), grid, dim3(256), 0, s, dy, ab, w, dab, T, C, ws, bn); \
+    if (use_gn && dz16) hipLaunchKernelGGL((glu_dwconv_bwd_vec_kernel<k, false, true, true>), grid, dim3(256), 0, s, dy, ab, w, dab, T, C, ws, bn); \
+    else if (use_gn) hipLaunchKernelGGL((glu_dwconv_bwd_vec_kernel<k, false, false, true>), grid, dim3(256), 0, s, dy, ab, w, dab, T, C, ws, bn); \
+    else if (!use_bn) hipLaunchKernelGGL((glu_dwconv_bwd_vec_kernel<k, false, false>), grid, dim3(256), 0, s, dy, ab, w, dab, T, C, ws, bn); \
     else if (dz16) hipLaunchKernelGGL((glu_dwconv_bwd_vec_kernel<k, true, true>), grid, dim3(256), 0, s, dy, ab, w, dab, T, C, ws, bn); \
     else hipLaunchKernelGGL((glu_dwconv_bwd_vec_kernel<k, true, false>), grid, dim3(256), 0, s, dy, ab, w, dab, T, C, ws, bn); \
     return true;
@@ -1019,6 +1220,99 @@ CFM_EXPORT int cfm_glu_dwconv_bwd_bn(const void* dz, int dtdz, const float* y, c
   cfm::colreduce(ws, (int)np, (long)C * (K + 1), sums, 0, s);
   hipLaunchKernelGGL(dwconv_scatter_kernel, dim3(cdiv((long)C * (K + 1), 256)), dim3(256), 0, s, sums, C, K, dw, db);
   return cfm::check_launch("cfm_glu_dwconv_bwd_bn");
+}
+
+// ----------------------------------------------------------------------------- GroupNorm(1, C) conv module
+namespace {
+// the (sum du, sum du*yhat) partials into ws, then both sets of results from them: per channel over all parts
+// (dbeta, dgamma), per sample with the gamma weights (coef = (k1, k2) rows)
+void gn_bwd_sums(const void* dz, int dtdz, const float* y, const float* gamma, const float* beta, const float* mean,
+                 const float* rstd, int B, int T, int C, float* ws, float* dbeta, float* dgamma, float* coef,
+                 hipStream_t s) {
+  const int nt = cdiv(T, TT);
+  const long np = conv_nparts(B, T);
+  hipLaunchKernelGGL(gn_bwd_sums_kernel, dim3(cdiv(C, CT), nt, B), dim3(256), 0, s, dz, dtdz, y, gamma, beta, mean,
+                     rstd, T, C, ws);
+  cfm::colreduce_pair(ws, ws + np * C, (int)np, C, dbeta, dgamma, s);
+  hipLaunchKernelGGL(gn_sample_kernel<true>, dim3(B), dim3(1024), 0, s, ws, ws + np * C, nt, C, gamma,
+                     1.0 / ((double)T * C), 0.f, coef, nullptr);
+}
+}  // namespace
+
+CFM_EXPORT int cfm_gn_silu_fwd(const float* y, const float* gamma, const float* beta, float eps, float* mean,
+                               float* rstd, void* z, int dtz, int B, int T, int C, const float* ws, void* stream) {
+  CFM_REQUIRE(y && gamma && beta && mean && rstd && z && ws, CFM_ERR_ARG, "null pointer");
+  CFM_REQUIRE(B > 0 && T > 0 && C > 0, CFM_ERR_SHAPE, "bad shape");
+  hipStream_t s = cfm::as_stream(stream);
+  const int nt = cdiv(T, TT);
+  const long np = conv_nparts(B, T), n = (long)B * T * C;
+  hipLaunchKernelGGL(gn_sample_kernel<false>, dim3(B), dim3(1024), 0, s, ws, ws + np * C, nt, C, nullptr,
+                     1.0 / ((double)T * C), eps, mean, rstd);
+  const bool vec = C % 8 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)z & 15) == 0 &&
+                   (dtz == CFM_BF16 || dtz == CFM_F32) && n / 8 / 256 < (1L << 31);
+  if (vec) {
+    const unsigned nb = (unsigned)((n / 8 + 255) / 256);
+    if (dtz == CFM_BF16)
+      hipLaunchKernelGGL(gn_apply_vec8<CFM_BF16>, dim3(nb), dim3(256), 0, s, y, gamma, beta, mean, rstd, z, B, T, C);
+    else
+      hipLaunchKernelGGL(gn_apply_vec8<CFM_F32>, dim3(nb), dim3(256), 0, s, y, gamma, beta, mean, rstd, z, B, T, C);
+  } else {
+    hipLaunchKernelGGL(gn_apply_kernel, dim3(ew_grid(n)), dim3(256), 0, s, y, gamma, beta, mean, rstd, z, dtz, B, T,
+                       C);
+  }
+  return cfm::check_launch("cfm_gn_silu_fwd");
+}
+
+CFM_EXPORT int cfm_gn_silu_bwd_sums(const void* dz, int dtdz, const float* y, const float* gamma, const float* beta,
+                                    const float* mean, const float* rstd, int B, int T, int C, float* ws,
+                                    float* dbeta, float* dgamma, float* coef, void* stream) {
+  CFM_REQUIRE(dz && y && gamma && beta && mean && rstd && ws && dbeta && dgamma && coef, CFM_ERR_ARG,
+              "null pointer");
+  CFM_REQUIRE(B > 0 && T > 0 && C > 0, CFM_ERR_SHAPE, "bad shape");
+  gn_bwd_sums(dz, dtdz, y, gamma, beta, mean, rstd, B, T, C, ws, dbeta, dgamma, coef, cfm::as_stream(stream));
+  return cfm::check_launch("cfm_gn_silu_bwd_sums");
+}
+
+CFM_EXPORT int cfm_gn_silu_bwd(const void* dz, int dtdz, const float* y, const float* gamma, const float* beta,
+                               const float* mean, const float* rstd, float* dy, float* dgamma, float* dbeta,
+                               float* coef, int B, int T, int C, float* ws, void* stream) {
+  CFM_REQUIRE(dz && y && gamma && beta && mean && rstd && dy && dgamma && dbeta && coef && ws, CFM_ERR_ARG,
+              "null pointer");
+  CFM_REQUIRE(B > 0 && T > 0 && C > 0, CFM_ERR_SHAPE, "bad shape");
+  hipStream_t s = cfm::as_stream(stream);
+  gn_bwd_sums(dz, dtdz, y, gamma, beta, mean, rstd, B, T, C, ws, dbeta, dgamma, coef, s);
+  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(ew_grid((long)B * T * C)), dim3(256), 0, s, dz, dtdz, y, gamma, beta,
+                     mean, rstd, coef, dy, B, T, C);
+  return cfm::check_launch("cfm_gn_silu_bwd");
+}
+
+CFM_EXPORT int cfm_glu_dwconv_bwd_gn(const void* dz, int dtdz, const float* y, const float* gamma, const float* beta,
+                                     const float* mean, const float* rstd, const float* coef, const void* a, int dta,
+                                     const float* w, void* da, int dtda, float* dw, float* db, int B, int T, int C,
+                                     int K, float* ws, void* stream) {
+  CFM_REQUIRE(dz && y && gamma && beta && mean && rstd && coef && a && w && da && ws, CFM_ERR_ARG, "null pointer");
+  CFM_REQUIRE(K >= 1 && K <= KMAX && (K % 2) == 1, CFM_ERR_UNSUPPORTED, "depthwise kernel must be odd and <= 63");
+  CFM_REQUIRE(B > 0 && T > 0 && C > 0, CFM_ERR_SHAPE, "bad shape");
+  dim3 grid(cdiv(C, CT), cdiv(T, TT), B);
+  size_t lds = (size_t)2 * (TT + K - 1) * CT * sizeof(float);
+  const size_t red = (size_t)4 * (K + 1) * CT * sizeof(float);
+  if (red > lds) lds = red;
+  hipStream_t s = cfm::as_stream(stream);
+  const BnBwd bn{dz, dtdz, y, gamma, beta, mean, rstd, nullptr, nullptr, 0.f, 1, coef};
+  if (!dwconv_bwd_vec(nullptr, a, dta, w, da, dtda, B, T, C, K, ws, bn, false, s, true)) switch (K) {
+#define X(k) case k: if (dta == CFM_BF16) hipLaunchKernelGGL((glu_dwconv_bwd_kernel<k, bf16, false, true>), grid, dim3(256), lds, s, nullptr, a, dta, w, da, dtda, T, C, K, ws, bn); \
+                    else hipLaunchKernelGGL((glu_dwconv_bwd_kernel<k, float, false, true>), grid, dim3(256), lds, s, nullptr, a, dta, w, da, dtda, T, C, K, ws, bn); break;
+    CFM_K_CASES(X)
+#undef X
+    default:
+      return cfm::fail(CFM_ERR_UNSUPPORTED, "cfm_glu_dwconv_bwd_gn: kernel size without a compiled variant");
+  }
+  if (!dw) return cfm::check_launch("cfm_glu_dwconv_bwd_gn");
+  const long np = conv_nparts(B, T);
+  float* sums = ws + np * (long)C * (K + 1);
+  cfm::colreduce(ws, (int)np, (long)C * (K + 1), sums, 0, s);
+  hipLaunchKernelGGL(dwconv_scatter_kernel, dim3(cdiv((long)C * (K + 1), 256)), dim3(256), 0, s, sums, C, K, dw, db);
+  return cfm::check_launch("cfm_glu_dwconv_bwd_gn");
 }
 
 CFM_EXPORT int cfm_glu_dwconv_bwd_wgrad(float* ws, int B, int T, int C, int K, float* dw, float* db, void* stream) {

@@ -8,6 +8,9 @@ MI355X build (documented in DESIGN.md):
   frontend_proj          'utterance' | 'frame'   reference whole-utterance Linear (asrnn.py:28)
                                                   or per-subsampled-frame Linear (scalable)
   pos_enc                'none' | 'rel'    torchaudio MHSA or Transformer-XL relative positions
+  use_group_norm         bool              GroupNorm(1, d) in place of BatchNorm1d in the Conformer conv module
+                                           (torchaudio's use_group_norm: per-utterance statistics, no running
+                                           statistics, no cross-replica reduce); default False
   specaug_ref_noop_masks bool              reproduce the reference's no-op masks (asrnn.py:141,165)
   dp_world_size          int               set by the data-parallel launcher
 """
@@ -53,8 +56,8 @@ _NST_LM = dict(nst=True, lm=False, train_lm=False, ft_lr=3e-6, ft_epochs=3, ft_t
                lm_in_N=4, lm_out_N=4, input_embedding_size=320, lm_in_mhsa_num_heads=8, lm_out_mhsa_num_heads=8,
                lm_masked_out_mhsa_num_heads=8, lm_innner_input_nodes=512, lm_innner_output_nodes=512, lm_epochs=3,
                lm_max_len=20, just_nst=True)
-_BUILD = dict(compute_dtype="bf16", frontend_proj="utterance", pos_enc="none", specaug_ref_noop_masks=False,
-              dp_world_size=1, layer_norm_eps=1e-5, bn_eps=1e-5, bn_momentum=0.1)
+_BUILD = dict(compute_dtype="bf16", frontend_proj="utterance", pos_enc="none", use_group_norm=False,
+              specaug_ref_noop_masks=False, dp_world_size=1, layer_norm_eps=1e-5, bn_eps=1e-5, bn_momentum=0.1)
 
 
 class HParams:

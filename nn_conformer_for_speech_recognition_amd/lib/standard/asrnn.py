@@ -56,6 +56,7 @@ class ASRNN(nn.Module):
             raise ValueError(f"frontend_proj must be 'utterance' or 'frame', got {self.frontend_proj!r}")
         self.conformers = Conformer(d, hp.mhsa_num_heads, hp.conformer_ff1_linear1_nodes, hp.n_conformers,
                                     hp.conformer_depthwise_conv_kernel, hp.dropout,
+                                    use_group_norm=bool(getattr(hp, "use_group_norm", False)),
                                     pos_enc=getattr(hp, "pos_enc", "none"), compute_dtype=self.compute_dtype)
         self.projection_fc = nn.Linear(d, hp.projection_out_size)
         self.swish = nn.SiLU()

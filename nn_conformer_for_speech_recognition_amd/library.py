@@ -15,6 +15,7 @@ Ops (SURVEY.md §3.3 block; the reference reaches them through torchaudio.models
   cfm::attention_rel / _bwd       the same with Transformer-XL relative positions (projected table pos, biases u / v:
                                   transformers modeling_wav2vec2_conformer.py:528-565, the rel-pos MFMA kernels)
   cfm::conv_glu_dwconv_bn_silu / _bwd   GLU -> depthwise Conv1d -> BatchNorm1d -> SiLU of the ConvModule
+  cfm::conv_glu_dwconv_gn_silu / _bwd   the same with GroupNorm(1, C) (use_group_norm=True; layer_forward picks)
   cfm::ctc_loss / _bwd            per-utterance CTC negative log-likelihood (log-probs, batch-first)
 
 `layer_forward` composes them into one torchaudio ConformerLayer; Conformer.forward takes that route
@@ -380,6 +381,73 @@ def _conv_backward(ctx, gz, _gy, _gm, _gi):
 conv_glu_dwconv_bn_silu.register_autograd(_conv_backward, setup_context=_conv_setup)
 
 
+@torch.library.custom_op("cfm::conv_glu_dwconv_gn_silu", mutates_args=(), device_types="cuda")
+def conv_glu_dwconv_gn_silu(a: Tensor, w_dw: Tensor, b_dw: Tensor, gamma: Tensor, beta: Tensor, eps: float, B: int,
+                            out_dtype: torch.dtype) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """ConvModule GLU -> depthwise Conv1d(K, 'same') -> GroupNorm(1, C) -> SiLU on token-major a (B*T, 2C)
+    (use_group_norm=True).  Returns (z (B*T, C) out_dtype, y (B*T, C) fp32 GroupNorm input, mean (B,), rstd (B,)):
+    per-utterance statistics over all T*C elements, padded frames included; the same function in train and eval."""
+    M, C2 = a.shape
+    C, K = w_dw.shape
+    T = M // B
+    ws = ops.convmod_ws(B, T, C, K, a.device)
+    y = ops.glu_dwconv_fwd(a.contiguous(), w_dw.contiguous(), b_dw, B, T, C, K, ws)
+    z, mean, rstd = ops.gn_silu_fwd(y, gamma, beta, eps, B, T, C, ws, out_dtype)
+    return z, y, mean, rstd
+
+
+@conv_glu_dwconv_gn_silu.register_fake
+def _(a, w_dw, b_dw, gamma, beta, eps, B, out_dtype):
+    M = a.shape[0]
+    C = w_dw.shape[0]
+    f = torch.float32
+    return a.new_empty(M, C, dtype=out_dtype), a.new_empty(M, C, dtype=f), a.new_empty(B, dtype=f), \
+        a.new_empty(B, dtype=f)
+
+
+@torch.library.custom_op("cfm::conv_glu_dwconv_gn_silu_bwd", mutates_args=(), device_types="cuda")
+def conv_glu_dwconv_gn_silu_bwd(dz: Tensor, a: Tensor, y: Tensor, w_dw: Tensor, gamma: Tensor, beta: Tensor,
+                                mean: Tensor, rstd: Tensor, B: int
+                                ) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """(da, dw_dw (C, K), db_dw, dgamma, dbeta), the GroupNorm input gradient folded into the depthwise backward
+    where the kernel size has a compiled variant."""
+    M = a.shape[0]
+    C, K = w_dw.shape
+    T = M // B
+    a, dz, w_dw = a.contiguous(), dz.contiguous(), w_dw.contiguous()
+    ws = ops.convmod_ws(B, T, C, K, a.device)
+    if K in ops.BN_FOLD_K:
+        da, dw, db, dg, dbt = ops.gn_silu_glu_dwconv_bwd(dz, y, gamma, beta, mean, rstd, a, w_dw, B, T, C, K, ws,
+                                                          a.dtype)
+    else:
+        dy, dg, dbt = ops.gn_silu_bwd(dz, y, gamma, beta, mean, rstd, B, T, ws)
+        da, dw, db = ops.glu_dwconv_bwd(dy, a, w_dw, B, T, C, K, ws, a.dtype)
+    return da, dw, db, dg.clone(), dbt.clone()
+
+
+@conv_glu_dwconv_gn_silu_bwd.register_fake
+def _(dz, a, y, w_dw, gamma, beta, mean, rstd, B):
+    C = w_dw.shape[0]
+    f = torch.float32
+    return a.new_empty(a.shape), w_dw.new_empty(w_dw.shape, dtype=f), a.new_empty(C, dtype=f), \
+        a.new_empty(C, dtype=f), a.new_empty(C, dtype=f)
+
+
+def _conv_gn_setup(ctx, inputs, output):
+    a, w_dw, _, gamma, beta, _, B, _ = inputs
+    ctx.save_for_backward(a, w_dw, gamma, beta, output[1], output[2], output[3])
+    ctx.B = B
+
+
+def _conv_gn_backward(ctx, gz, _gy, _gm, _gi):
+    a, w_dw, gamma, beta, y, mean, rstd = ctx.saved_tensors
+    da, dw, db, dg, dbt = torch.ops.cfm.conv_glu_dwconv_gn_silu_bwd(gz, a, y, w_dw, gamma, beta, mean, rstd, ctx.B)
+    return da, dw.to(w_dw.dtype), db, dg, dbt, None, None, None
+
+
+conv_glu_dwconv_gn_silu.register_autograd(_conv_gn_backward, setup_context=_conv_gn_setup)
+
+
 # ----------------------------------------------------------------------------- CTC
 @torch.library.custom_op("cfm::ctc_loss", mutates_args=(), device_types="cuda")
 def ctc_loss(log_probs: Tensor, targets: Tensor, input_lengths: Tensor, target_lengths: Tensor, blank: int,
@@ -467,6 +535,9 @@ def layer_forward(layer, x, lens, B, T, cd, seed):
         bn = layer.conv_module.sequential[3]
         xn, _, _ = cfm.layer_norm(x, P[12], P[13], _EPS, cd)
         a = cfm.linear(xn, P[14].view(2 * d, d), P[15], None, 0.0, 0, 1.0, cd)
+        if layer.use_group_norm:
+            z = cfm.conv_glu_dwconv_gn_silu(a, P[16].view(d, K), P[17], P[18], P[19], bn.eps, B, cd)[0]
+            return cfm.linear(z, P[20].view(d, d), P[21], x, p, s, 1.0, f32)
         train = layer.training or not bn.track_running_stats
         z, _, mean, invstd = cfm.conv_glu_dwconv_bn_silu(
             a, P[16].view(d, K), P[17], P[18], P[19], None if train else bn.running_mean,

@@ -829,6 +829,49 @@ def bn_silu_glu_dwconv_bwd(dz, y, gamma, beta, mean, invstd, training, a, w_dw, 
     return da, dw, db, dbg[1], dbg[0]
 
 
+def gn_silu_fwd(y, gamma, beta, eps, B, T, C, ws, out_dtype):
+    """z = silu(GroupNorm(1, C)(y)): per-sample statistics over all T*C elements (padded frames included), from
+    the (sum, sumsq) partials cfm_glu_dwconv_fwd left in ws.  Returns (z, mean (B,), rstd (B,))."""
+    mean = torch.empty(B, device=y.device, dtype=torch.float32)
+    rstd = torch.empty(B, device=y.device, dtype=torch.float32)
+    z = torch.empty(B * T, C, device=y.device, dtype=out_dtype)
+    L.call("cfm_gn_silu_fwd", L.ptr(y), L.ptr(gamma), L.ptr(beta), float(eps), L.ptr(mean), L.ptr(rstd), L.ptr(z),
+           L.dt(z), B, T, C, L.ptr(ws), L.stream())
+    return z, mean, rstd
+
+
+def gn_silu_bwd(dz, y, gamma, beta, mean, rstd, B, T, ws):
+    """Unfused GroupNorm + SiLU backward (any depthwise kernel size): (dy fp32, dgamma, dbeta)."""
+    C = y.shape[1]
+    dy = torch.empty(B * T, C, device=y.device, dtype=torch.float32)
+    dbg = torch.empty(2, C, device=y.device, dtype=torch.float32)     # [dbeta; dgamma]
+    coef = torch.empty(B, 2, device=y.device, dtype=torch.float32)
+    L.call("cfm_gn_silu_bwd", L.ptr(dz), L.dt(dz), L.ptr(y), L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(rstd),
+           L.ptr(dy), L.ptr(dbg[1]), L.ptr(dbg[0]), L.ptr(coef), B, T, C, L.ptr(ws), L.stream())
+    return dy, dbg[1], dbg[0]
+
+
+def gn_silu_glu_dwconv_bwd(dz, y, gamma, beta, mean, rstd, a, w_dw, B, T, C, K, ws, da_dtype, side=None):
+    """GroupNorm(1, C) + SiLU backward folded into the GLU + depthwise-conv backward (cfm_glu_dwconv_bwd_gn): the
+    parameter gradients and the per-sample coefficients (k1, k2) come from cfm_gn_silu_bwd_sums, the GroupNorm
+    input gradient is formed inside the depthwise kernel and never stored.  side: as bn_silu_glu_dwconv_bwd.
+    Returns (da, dw_dw, db_dw, dgamma, dbeta)."""
+    M = B * T
+    dbg = torch.empty(2, C, device=y.device, dtype=torch.float32)     # [dbeta; dgamma]
+    coef = torch.empty(B, 2, device=y.device, dtype=torch.float32)    # not in ws: the depthwise kernel overwrites it
+    L.call("cfm_gn_silu_bwd_sums", L.ptr(dz), L.dt(dz), L.ptr(y), L.ptr(gamma), L.ptr(beta), L.ptr(mean),
+           L.ptr(rstd), B, T, C, L.ptr(ws), L.ptr(dbg[0]), L.ptr(dbg[1]), L.ptr(coef), L.stream())
+    da = torch.empty(M, 2 * C, device=a.device, dtype=da_dtype)
+    dw = torch.empty(C, K, device=a.device, dtype=torch.float32)
+    db = torch.empty(C, device=a.device, dtype=torch.float32)
+    defer = side is not None
+    L.call("cfm_glu_dwconv_bwd_gn", L.ptr(dz), L.dt(dz), L.ptr(y), L.ptr(gamma), L.ptr(beta), L.ptr(mean),
+           L.ptr(rstd), L.ptr(coef), L.ptr(a), L.dt(a), L.ptr(w_dw), L.ptr(da), L.dt(da),
+           None if defer else L.ptr(dw), None if defer else L.ptr(db), B, T, C, K, L.ptr(ws), L.stream())
+    da, dw, db = _dwconv_wgrad(ws, B, T, C, K, da, dw, db, side)
+    return da, dw, db, dbg[1], dbg[0]
+
+
 def _dwconv_wgrad(ws, B, T, C, K, da, dw, db, side):
     defer = side is not None
     if defer:
