@@ -651,6 +651,36 @@ int cfm_adafactor_step(const void* dev_table, int n, long nrow_tasks, long ncols
                        long nrowmean_tasks, long ncolpart_tasks, float* rowmean, float* part,
                        float* partial, float lr, float beta1, float beta2t, float eps1, float clip,
                        void* stream);
+/* The rest of transformers.Adafactor on the same table, tasks and buffers: scale_parameter,
+ * weight_decay, and a step whose scalars live on the device (graph-capturable).  Per tensor
+ *   lr_p = rel * (SCALE_PARAMETER ? max(eps2, RMS(p)) : 1),   RMS(p) = ||p|| / sqrt(numel) of p
+ *          before this step (written to rms_out[i], i = table index; per-block sums of p^2 in
+ *          partial_p, >= nblocks floats, summed in block order as `partial` is),
+ *   p += -weight_decay * lr_p * p  before  p -= update.
+ * Without DEVICE_STEP rel = lr and beta2t is the argument, as in cfm_adafactor_step (the host has
+ * resolved a relative step already; RELATIVE_STEP / WARMUP_INIT are not read).  With DEVICE_STEP
+ * one extra launch increments *step_dev (int32) and writes scalars_dev[0] = beta2t =
+ * 1 - step^decay_rate and scalars_dev[1] = rel = RELATIVE_STEP ? min(WARMUP_INIT ? 1e-6 step :
+ * 1e-2, 1/sqrt(step)) : lr (both computed in double, rounded once), which the other kernels read:
+ * no host value depends on the step, so one captured launch sequence replays as successive steps.
+ * flags == 0 and weight_decay == 0 launches exactly what cfm_adafactor_step launches. */
+enum cfm_adafactor_flags {
+  CFM_ADA_SCALE_PARAMETER = 1 << 0,
+  CFM_ADA_RELATIVE_STEP = 1 << 1,
+  CFM_ADA_WARMUP_INIT = 1 << 2,
+  CFM_ADA_DEVICE_STEP = 1 << 3
+};
+typedef struct {
+  double decay_rate;   /* DEVICE_STEP only */
+  float lr, beta1, beta2t, eps1, eps2, clip, weight_decay;
+  int flags;           /* cfm_adafactor_flags */
+  int* step_dev;       /* DEVICE_STEP: one int32, incremented by the call */
+  float* scalars_dev;  /* DEVICE_STEP: 2 floats */
+} cfm_adafactor_hyper;
+int cfm_adafactor_step_ex(const void* dev_table, int n, long nrow_tasks, long ncols, long nblocks,
+                          long nrowmean_tasks, long ncolpart_tasks, float* rowmean, float* part,
+                          float* partial, float* partial_p, float* rms_out,
+                          const cfm_adafactor_hyper* hyper, void* stream);
 
 /* ---------------------------------------------------------------- CTC head (runner.py:35,142-143)
  * Replaces torch.nn.CTCLoss(blank=hp.blank_idx, zero_infinity=True) on

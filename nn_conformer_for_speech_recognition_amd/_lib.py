@@ -98,6 +98,17 @@ class FfoldGeo(ctypes.Structure):
         ("xt_elems", c_long), ("ws_floats", c_long)]
 
 
+class AdafactorHyper(ctypes.Structure):
+    """cfm_adafactor_hyper (include/cfm.h): what cfm_adafactor_step_ex takes beyond the table and the buffers."""
+    _fields_ = [("decay_rate", ctypes.c_double)] + [(n, c_float) for n in (
+        "lr", "beta1", "beta2t", "eps1", "eps2", "clip", "weight_decay")] + [
+        ("flags", c_int), ("step_dev", c_void_p), ("scalars_dev", c_void_p)]
+
+
+# cfm_adafactor_flags
+ADA_SCALE_PARAMETER, ADA_RELATIVE_STEP, ADA_WARMUP_INIT, ADA_DEVICE_STEP = 1, 2, 4, 8
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "cfm_version": (c_int, []),
@@ -190,6 +201,9 @@ _SIGS = {
     "cfm_adafactor_rowmean_tasks": (c_long, [c_int, c_int]),
     "cfm_adafactor_step": (c_int, [c_void_p, c_int, c_long, c_long, c_long, c_long, c_long, c_void_p, c_void_p,
                                    c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p]),
+    # (..., rowmean, part, partial, partial_p, rms_out, const cfm_adafactor_hyper*, stream)
+    "cfm_adafactor_step_ex": (c_int, [c_void_p, c_int, c_long, c_long, c_long, c_long, c_long, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cfm_silu_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_long, c_void_p]),
     "cfm_bn_ws_bytes": (c_size_t, [c_int]),
     "cfm_bn_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_void_p,

@@ -12,6 +12,12 @@
 // tensor's partials in block order: deterministic, no atomics).  float4 paths where aligned.  Work items are "tasks" whose shape
 // adapts to the tensor: a wide row (C >= 64) is one wave, narrow rows (e.g. the 3x3 taps of the
 // conv2 weight, nb = 65536) are packed 64 per wave (one per lane).  HBM-bound.
+//
+// cfm_adafactor_step_ex adds the rest of transformers.Adafactor to the same launches: scale_parameter (the step
+// size times max(eps2, RMS(p)); the u^2 pass also sums p^2 per block), weight_decay, and a device-side step
+// (ada_scalars: step count, beta2t and relative step size in device memory, so a captured launch sequence
+// replays as successive steps).  All of it is compile-time variants: the kernels cfm_adafactor_step launches
+// (<float>, <false>) have the instruction stream they had before the variants existed.
 #include "cfm_common.h"
 
 namespace {
@@ -61,6 +67,12 @@ __device__ __forceinline__ int find_param(const AdaP* t, int n, long idx, int wh
   return lo;
 }
 
+// beta2t reaches a kernel as the host's float (B2 = float: the kernels cfm_adafactor_step launches), or is read
+// from the device step scalars that ada_scalars writes (B2 = const float*: the capturable step)
+constexpr int SC_B2T = 0, SC_REL = 1;   // scalar block: beta2t, relative step size
+__device__ __forceinline__ float b2t_of(float v) { return v; }
+__device__ __forceinline__ float b2t_of(const float* sc) { return sc[SC_B2T]; }
+
 __device__ __forceinline__ void row_update(const AdaP& q, long lr, float s, float b2t) {
   q.row[lr] = b2t * q.row[lr] + (1.f - b2t) * (s / q.C);
 }
@@ -68,8 +80,10 @@ __device__ __forceinline__ void row_update(const AdaP& q, long lr, float s, floa
 // Wide factored tensors (64 <= C <= 2560), one pass over g: task (b, rb) covers rows
 // rb*RB .. rb*RB+RB-1 of matrix b.  Row statistics are finished here (wave reduction per row);
 // column sums of the block go to part[b][rb][c] (finished by ada_cols, fixed order).
-__global__ __launch_bounds__(EB) void ada_colpart(const AdaP* __restrict__ t, int n, long ntasks, float b2t,
+template <class B2>
+__global__ __launch_bounds__(EB) void ada_colpart(const AdaP* __restrict__ t, int n, long ntasks, B2 b2,
                                                   float eps1, float* __restrict__ part) {
+  const float b2t = b2t_of(b2);
   __shared__ float red[4][64 * KMAX];
   const long task = blockIdx.x;
   if (task >= ntasks) return;
@@ -161,7 +175,9 @@ __global__ __launch_bounds__(EB) void ada_colpart(const AdaP* __restrict__ t, in
 // parameter search -- ~9 dependent table loads -- in front of one 4-byte row: ~18.6 M such rows at L15, the
 // degenerate (O, I, 1) pointwise-conv weights, ran 95 us)
 constexpr int ROWS_PER_TASK = 256;
-__global__ void ada_rows(const AdaP* __restrict__ t, int n, long ntasks, float b2t, float eps1) {
+template <class B2>
+__global__ void ada_rows(const AdaP* __restrict__ t, int n, long ntasks, B2 b2, float eps1) {
+  const float b2t = b2t_of(b2);
   const int lane = threadIdx.x & 63;
   // wave-uniform task made provably uniform: the parameter search and the table fields become scalar loads
   const long task = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -204,8 +220,10 @@ __global__ void ada_rows(const AdaP* __restrict__ t, int n, long ntasks, float b
 
 // one thread per factored column: col = b2t*col + (1-b2t)*mean_r(g^2 + eps1)
 // wide: sum of the ada_colpart partials in row-block order; narrow: direct sum over the R rows
-__global__ void ada_cols(const AdaP* __restrict__ t, int n, long ncols, float b2t, float eps1,
+template <class B2>
+__global__ void ada_cols(const AdaP* __restrict__ t, int n, long ncols, B2 b2, float eps1,
                          const float* __restrict__ part) {
+  const float b2t = b2t_of(b2);
   const long cidx = (long)blockIdx.x * EB + threadIdx.x;
   if (cidx >= ncols) return;
   // the block's first column's parameter by a uniform (scalar) search, then a short per-lane forward scan
@@ -309,15 +327,32 @@ __device__ __forceinline__ bool vec4_ok(const AdaP& q) {
          (q.factored || (uintptr_t)q.row % 16 == 0);
 }
 
+// What scale_parameter / weight_decay / the device step add to the two elementwise kernels, as a trailing kernel
+// argument that is empty without them (<false>: the kernels cfm_adafactor_step launches; no extra load or store).
+template <bool PRMS> struct SumsqEx {};
+template <> struct SumsqEx<true> { float* partial_p; };   // per-block sums of p^2
+template <bool EX> struct ApplyEx {};
+// rel = sc ? sc[SC_REL] : lr;  lr_p = rel * (partial_p ? max(eps2, RMS(p)) : 1), RMS(p) -> rms_out[param];
+// p += -wd * lr_p * p before p -= update  (transformers.Adafactor._get_lr and its weight decay)
+template <> struct ApplyEx<true> {
+  const float* partial_p; const float* sc; float* rms_out;
+  float eps2, wd;
+};
+
 // per-block sum of u^2 -> partial[blk] (summed in block order by ada_apply: deterministic)
+// PRMS (scale_parameter): the same pass reads p and writes the block's sum of p^2 -> partial_p[blk]; that is p
+// before this step's update, which ada_apply makes in the next launch.
+template <bool PRMS, class B2>
 __global__ __launch_bounds__(EB) void ada_sumsq(const AdaP* __restrict__ t, int n, const float* __restrict__ rowmean,
-                                                float b2t, float eps1, float* __restrict__ partial) {
+                                                B2 b2, float eps1, float* __restrict__ partial, SumsqEx<PRMS> ex) {
+  const float b2t = b2t_of(b2);
   __shared__ float red[EB / 64];
+  __shared__ float redp[PRMS ? EB / 64 : 1];
   const int pi = find_param(t, n, blockIdx.x, 2);
   const AdaP& q = t[pi];
   const long start = (long)(blockIdx.x - q.blk_off) * CHUNK;
   const long end = min(q.numel, start + CHUNK);
-  float s = 0.f;
+  float s = 0.f, sp = 0.f;
   if (vec4_ok(q)) {
     // CHUNK / (4 EB) = 4 float4 steps per thread, unrolled: their loads are in flight together
 #pragma unroll
@@ -327,6 +362,10 @@ __global__ __launch_bounds__(EB) void ada_sumsq(const AdaP* __restrict__ t, int 
         float u[4];
         ada_u<4>(q, rowmean, (unsigned)i, b2t, eps1, true, u);
         s += u[0] * u[0] + u[1] * u[1] + u[2] * u[2] + u[3] * u[3];
+        if constexpr (PRMS) {
+          const float4 p = *reinterpret_cast<const float4*>(q.p + i);
+          sp += p.x * p.x + p.y * p.y + p.z * p.z + p.w * p.w;
+        }
       }
     }
   } else {
@@ -334,18 +373,28 @@ __global__ __launch_bounds__(EB) void ada_sumsq(const AdaP* __restrict__ t, int 
       float u[1];
       ada_u<1>(q, rowmean, (unsigned)i, b2t, eps1, true, u);
       s += u[0] * u[0];
+      if constexpr (PRMS) sp += q.p[i] * q.p[i];
     }
   }
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  if constexpr (PRMS) {
+    sp = wave_sum(sp);
+    if ((threadIdx.x & 63) == 0) redp[threadIdx.x >> 6] = sp;
+  }
   __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  if constexpr (PRMS) {
+    if (threadIdx.x == 0) ex.partial_p[blockIdx.x] = redp[0] + redp[1] + redp[2] + redp[3];
+  }
 }
 
+template <bool EX>
 __global__ __launch_bounds__(EB) void ada_apply(const AdaP* __restrict__ t, int n, const float* __restrict__ rowmean,
                                                 float b2t, float eps1, const float* __restrict__ partial, float lr,
-                                                float beta1, float clip) {
+                                                float beta1, float clip, ApplyEx<EX> ex) {
   __shared__ float red[EB / 64];
+  __shared__ float redp[EX ? EB / 64 : 1];
   const int pi = find_param(t, n, blockIdx.x, 2);
   const AdaP& q = t[pi];
   // RMS(u) of the whole tensor: its blocks' partials in block order
@@ -354,11 +403,30 @@ __global__ __launch_bounds__(EB) void ada_apply(const AdaP* __restrict__ t, int 
   for (int k = threadIdx.x; k < nblk; k += EB) ps += partial[q.blk_off + k];
   ps = wave_sum(ps);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ps;
+  if constexpr (EX) {
+    if (ex.partial_p) {   // RMS(p): the same fixed order
+      float pp = 0.f;
+      for (int k = threadIdx.x; k < nblk; k += EB) pp += ex.partial_p[q.blk_off + k];
+      pp = wave_sum(pp);
+      if ((threadIdx.x & 63) == 0) redp[threadIdx.x >> 6] = pp;
+    }
+  }
   __syncthreads();
   const float sumsq = red[0] + red[1] + red[2] + red[3];
   const long start = (long)(blockIdx.x - q.blk_off) * CHUNK;
   const long end = min(q.numel, start + CHUNK);
   const float rms = sqrtf(sumsq / (float)q.numel);
+  [[maybe_unused]] float decay = 0.f;
+  if constexpr (EX) {
+    if (ex.sc) lr = ex.sc[SC_REL];
+    if (ex.partial_p) {
+      const float rms_p = sqrtf((redp[0] + redp[1] + redp[2] + redp[3]) / (float)q.numel);
+      lr *= fmaxf(ex.eps2, rms_p);
+      // every block of the tensor holds the same value; its first block stores it
+      if (blockIdx.x == q.blk_off && threadIdx.x == 0) ex.rms_out[pi] = rms_p;
+    }
+    decay = -ex.wd * lr;
+  }
   const float scale = lr / fmaxf(rms / clip, 1.f);
   if (vec4_ok(q)) {
     // the CHUNK / (4 EB) = 4 steps unrolled with every load (g, factors, m, p) issued before the first store: vmcnt
@@ -389,6 +457,9 @@ __global__ __launch_bounds__(EB) void ada_apply(const AdaP* __restrict__ t, int 
         *reinterpret_cast<float4*>(q.m + i) = upd;
       }
       float4 p = pv[j];
+      if constexpr (EX) {
+        if (ex.wd != 0.f) { p.x += decay * p.x; p.y += decay * p.y; p.z += decay * p.z; p.w += decay * p.w; }
+      }
       p.x -= upd.x; p.y -= upd.y; p.z -= upd.z; p.w -= upd.w;
       *reinterpret_cast<float4*>(q.p + i) = p;
     }
@@ -401,9 +472,25 @@ __global__ __launch_bounds__(EB) void ada_apply(const AdaP* __restrict__ t, int 
         upd = beta1 * q.m[i] + (1.f - beta1) * upd;
         q.m[i] = upd;
       }
+      if constexpr (EX) {
+        if (ex.wd != 0.f) q.p[i] += decay * q.p[i];
+      }
       q.p[i] -= upd;
     }
   }
+}
+
+// The device step (capturable): ++*step, then the two scalars the host path computes from its Python step count,
+// in double as the host does (math.pow / math.sqrt, rounded to float once).  One thread.
+__global__ void ada_scalars(int* __restrict__ step, float* __restrict__ sc, double decay_rate, float lr, int relative,
+                            int warmup) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const int s = *step + 1;
+  *step = s;
+  sc[SC_B2T] = (float)(1.0 - pow((double)s, decay_rate));
+  double rel = lr;
+  if (relative) rel = fmin(warmup ? 1e-6 * s : 1e-2, 1.0 / sqrt((double)s));
+  sc[SC_REL] = (float)rel;
 }
 
 }  // namespace
@@ -445,17 +532,69 @@ CFM_EXPORT int cfm_adafactor_step(const void* dev_table, int n, long nrow_tasks,
   const AdaP* t = reinterpret_cast<const AdaP*>(dev_table);
   hipStream_t s = cfm::as_stream(stream);
   if (ncp_tasks > 0)
-    hipLaunchKernelGGL(ada_colpart, dim3((unsigned)ncp_tasks), dim3(EB), 0, s, t, n, ncp_tasks, beta2t, eps1, part);
-  if (nrow_tasks > 0)
-    hipLaunchKernelGGL(ada_rows, dim3((unsigned)((nrow_tasks + 3) / 4)), dim3(256), 0, s, t, n, nrow_tasks, beta2t,
-                       eps1);
-  if (ncols > 0)
-    hipLaunchKernelGGL(ada_cols, dim3((unsigned)((ncols + EB - 1) / EB)), dim3(EB), 0, s, t, n, ncols, beta2t, eps1,
+    hipLaunchKernelGGL(ada_colpart<float>, dim3((unsigned)ncp_tasks), dim3(EB), 0, s, t, n, ncp_tasks, beta2t, eps1,
                        part);
+  if (nrow_tasks > 0)
+    hipLaunchKernelGGL(ada_rows<float>, dim3((unsigned)((nrow_tasks + 3) / 4)), dim3(256), 0, s, t, n, nrow_tasks,
+                       beta2t, eps1);
+  if (ncols > 0)
+    hipLaunchKernelGGL(ada_cols<float>, dim3((unsigned)((ncols + EB - 1) / EB)), dim3(EB), 0, s, t, n, ncols, beta2t,
+                       eps1, part);
   if (nrm_tasks > 0)
     hipLaunchKernelGGL(ada_rowmean, dim3((unsigned)((nrm_tasks + 3) / 4)), dim3(256), 0, s, t, n, nrm_tasks, rowmean);
-  hipLaunchKernelGGL(ada_sumsq, dim3((unsigned)nblocks), dim3(EB), 0, s, t, n, rowmean, beta2t, eps1, partial);
-  hipLaunchKernelGGL(ada_apply, dim3((unsigned)nblocks), dim3(EB), 0, s, t, n, rowmean, beta2t, eps1, partial, lr,
-                     beta1, clip);
+  hipLaunchKernelGGL((ada_sumsq<false, float>), dim3((unsigned)nblocks), dim3(EB), 0, s, t, n, rowmean, beta2t, eps1,
+                     partial, SumsqEx<false>{});
+  hipLaunchKernelGGL(ada_apply<false>, dim3((unsigned)nblocks), dim3(EB), 0, s, t, n, rowmean, beta2t, eps1, partial,
+                     lr, beta1, clip, ApplyEx<false>{});
   return cfm::check_launch("cfm_adafactor_step");
+}
+
+CFM_EXPORT int cfm_adafactor_step_ex(const void* dev_table, int n, long nrow_tasks, long ncols, long nblocks,
+                                     long nrm_tasks, long ncp_tasks, float* rowmean, float* part, float* partial,
+                                     float* partial_p, float* rms_out, const cfm_adafactor_hyper* h, void* stream) {
+  CFM_REQUIRE(h, CFM_ERR_ARG, "null hyper-parameters");
+  const bool dev = h->flags & CFM_ADA_DEVICE_STEP, scale = h->flags & CFM_ADA_SCALE_PARAMETER;
+  CFM_REQUIRE(!dev || (h->step_dev && h->scalars_dev), CFM_ERR_ARG, "device step without step / scalar pointers");
+  CFM_REQUIRE(!scale || (partial_p && rms_out), CFM_ERR_ARG, "scale_parameter without the p^2 partial / RMS buffers");
+  if (!dev && !scale && h->weight_decay == 0.f)   // nothing to add: the very same launches
+    return cfm_adafactor_step(dev_table, n, nrow_tasks, ncols, nblocks, nrm_tasks, ncp_tasks, rowmean, part, partial,
+                              h->lr, h->beta1, h->beta2t, h->eps1, h->clip, stream);
+  CFM_REQUIRE(dev_table && rowmean && partial && n > 0 && (ncp_tasks == 0 || part), CFM_ERR_ARG, "bad args");
+  const AdaP* t = reinterpret_cast<const AdaP*>(dev_table);
+  hipStream_t s = cfm::as_stream(stream);
+  const float* sc = h->scalars_dev;
+  const float b2t = h->beta2t, eps1 = h->eps1;
+  const dim3 g_cp((unsigned)ncp_tasks), g_rows((unsigned)((nrow_tasks + 3) / 4)),
+      g_cols((unsigned)((ncols + EB - 1) / EB)), g_blk((unsigned)nblocks);
+  if (dev) {
+    hipLaunchKernelGGL(ada_scalars, dim3(1), dim3(64), 0, s, h->step_dev, h->scalars_dev, h->decay_rate, h->lr,
+                       (int)((h->flags & CFM_ADA_RELATIVE_STEP) != 0), (int)((h->flags & CFM_ADA_WARMUP_INIT) != 0));
+    if (ncp_tasks > 0)
+      hipLaunchKernelGGL(ada_colpart<const float*>, g_cp, dim3(EB), 0, s, t, n, ncp_tasks, sc, eps1, part);
+    if (nrow_tasks > 0) hipLaunchKernelGGL(ada_rows<const float*>, g_rows, dim3(256), 0, s, t, n, nrow_tasks, sc, eps1);
+    if (ncols > 0) hipLaunchKernelGGL(ada_cols<const float*>, g_cols, dim3(EB), 0, s, t, n, ncols, sc, eps1, part);
+  } else {
+    if (ncp_tasks > 0) hipLaunchKernelGGL(ada_colpart<float>, g_cp, dim3(EB), 0, s, t, n, ncp_tasks, b2t, eps1, part);
+    if (nrow_tasks > 0) hipLaunchKernelGGL(ada_rows<float>, g_rows, dim3(256), 0, s, t, n, nrow_tasks, b2t, eps1);
+    if (ncols > 0) hipLaunchKernelGGL(ada_cols<float>, g_cols, dim3(EB), 0, s, t, n, ncols, b2t, eps1, part);
+  }
+  if (nrm_tasks > 0)
+    hipLaunchKernelGGL(ada_rowmean, dim3((unsigned)((nrm_tasks + 3) / 4)), dim3(256), 0, s, t, n, nrm_tasks, rowmean);
+  if (scale && dev)
+    hipLaunchKernelGGL((ada_sumsq<true, const float*>), g_blk, dim3(EB), 0, s, t, n, rowmean, sc, eps1, partial,
+                       SumsqEx<true>{partial_p});
+  else if (scale)
+    hipLaunchKernelGGL((ada_sumsq<true, float>), g_blk, dim3(EB), 0, s, t, n, rowmean, b2t, eps1, partial,
+                       SumsqEx<true>{partial_p});
+  else if (dev)
+    hipLaunchKernelGGL((ada_sumsq<false, const float*>), g_blk, dim3(EB), 0, s, t, n, rowmean, sc, eps1, partial,
+                       SumsqEx<false>{});
+  else
+    hipLaunchKernelGGL((ada_sumsq<false, float>), g_blk, dim3(EB), 0, s, t, n, rowmean, b2t, eps1, partial,
+                       SumsqEx<false>{});
+  // (the apply pass does not read beta2t: ada_sumsq has updated the second moments)
+  hipLaunchKernelGGL(ada_apply<true>, g_blk, dim3(EB), 0, s, t, n, rowmean, b2t, eps1, partial, h->lr, h->beta1,
+                     h->clip, ApplyEx<true>{scale ? partial_p : nullptr, dev ? sc : nullptr, rms_out, h->eps2,
+                                            h->weight_decay});
+  return cfm::check_launch("cfm_adafactor_step_ex");
 }

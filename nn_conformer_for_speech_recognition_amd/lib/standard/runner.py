@@ -5,7 +5,7 @@ Same constructor, methods and control flow as the reference; what runs underneat
 
   loss         ctc.CTCLoss(blank=hp.blank_idx, zero_infinity=True)  (runner.py:35; libcfm CTC kernels)
   optimizer    optim.Adafactor(lr=hp.lr, beta1, scale_parameter, relative_step)  (runner.py:36; one
-               multi-tensor HIP step)
+               multi-tensor HIP step; hp.scale_parameter / hp.relative_step True run on the device too)
   predict      ASRNN.predict -> cfm_ctc_greedy_decode (device argmax, torch.argmax tie rule)
   labels       generate_labels (runner.py:253-281): eval-mode forward (BatchNorm running stats, no
                dropout) -> device greedy decode with <pad>/<blank> stripped ON the device (no repeat

@@ -3,9 +3,21 @@
 relative_step=False)``) as ONE multi-tensor HIP step over all parameters (csrc/optim.hip) instead
 of ~10 small PyTorch kernels per tensor.
 
-Same constructor signature and state keys as transformers' Adafactor (exp_avg, exp_avg_sq_row,
-exp_avg_sq_col / exp_avg_sq, step).  Supported on the device path: relative_step (host-side
-learning-rate schedule), warmup_init; not supported (raise): scale_parameter=True, weight_decay.
+Same constructor signature, defaults and state keys as transformers' Adafactor (exp_avg,
+exp_avg_sq_row, exp_avg_sq_col / exp_avg_sq, step, RMS), every option on the device path:
+relative_step and warmup_init (the learning-rate schedule), scale_parameter (the step is scaled by
+max(eps[1], RMS(p)) per tensor; RMS(p) is summed in the pass that already sums the update's
+squares) and weight_decay.  ``state[p]["RMS"]`` is a 0-d device tensor with scale_parameter=True
+(a view of one buffer per group, refreshed by every step without a host sync) and stays 0 without
+it: nothing reads it then, and the scale_parameter=False step loads nothing for it.
+
+``capturable=True`` (torch.optim's name) makes ``step()`` free of host-dependent scalars: the
+group's step count is one device int32 (``state[p]["step"]`` is a view of it), incremented by the
+step itself, and beta2t and the relative step size are computed from it on the device.  One eager
+warm-up step builds and uploads the task table and the buffers; after it ``step()`` makes no
+host-to-device copy and may be captured into a HIP graph and replayed, with the gradients written
+into the same ``.grad`` buffers.  Without it the scalars come from the Python step count, as
+before.  All parameters of a group share one step count (either way).
 """
 from __future__ import annotations
 
@@ -16,27 +28,32 @@ import torch
 
 from . import _lib as L
 
+_NEEDS_WARMUP = ("libcfm Adafactor: one eager warm-up step builds and uploads the table and buffers; "
+                 "then step() may be captured and replayed")
+
 
 class Adafactor(torch.optim.Optimizer):
     def __init__(self, params, lr=None, eps=(1e-30, 1e-3), clip_threshold=1.0, decay_rate=-0.8, beta1=None,
-                 weight_decay=0.0, scale_parameter=True, relative_step=True, warmup_init=False):
+                 weight_decay=0.0, scale_parameter=True, relative_step=True, warmup_init=False, capturable=False):
         if lr is not None and relative_step:
             raise ValueError("Cannot combine manual `lr` and `relative_step=True` options")
         if warmup_init and not relative_step:
             raise ValueError("`warmup_init=True` requires `relative_step=True`")
-        if scale_parameter:
-            raise NotImplementedError("libcfm Adafactor: scale_parameter=True is not on the device path "
-                                      "(the reference uses scale_parameter=False, runner.py:36)")
-        if weight_decay != 0.0:
-            raise NotImplementedError("libcfm Adafactor: weight_decay is not on the device path")
         defaults = dict(lr=lr, eps=eps, clip_threshold=clip_threshold, decay_rate=decay_rate, beta1=beta1,
                         weight_decay=weight_decay, scale_parameter=scale_parameter, relative_step=relative_step,
-                        warmup_init=warmup_init)
+                        warmup_init=warmup_init, capturable=capturable)
         super().__init__(params, defaults)
         self._step = 0
         self._dev = {}
         self._tables = {}
         self._fast = {}
+        self._gbuf = {}     # per (group, device): RMS(p) per parameter; step counter and scalars if capturable
+        self._stepped = set()   # ids of the device step counters that have counted a step
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:     # a state dict saved before the keyword existed (or by transformers)
+            group.setdefault("capturable", False)
 
     @staticmethod
     def _geom(p):
@@ -44,6 +61,19 @@ class Adafactor(torch.optim.Optimizer):
             R, C = p.shape[-2], p.shape[-1]
             return True, p.numel() // (R * C), R, C
         return False, 1, 1, p.numel()
+
+    def _group_buffers(self, group, dev):
+        """(rms, step, scalars) of a group: rms one float per parameter of the group (state["RMS"] views
+        it); step (int32) and the two device scalars only when capturable."""
+        key = (id(group), dev)
+        gb = self._gbuf.get(key)
+        if gb is None:
+            rms = torch.zeros(len(group["params"]), device=dev)
+            cap = group["capturable"]
+            gb = (rms, torch.zeros((), dtype=torch.int32, device=dev) if cap else None,
+                  torch.zeros(2, device=dev) if cap else None)
+            self._gbuf[key] = gb
+        return gb
 
     def _ensure_state(self, p, group):
         st = self.state[p]
@@ -80,6 +110,33 @@ class Adafactor(torch.optim.Optimizer):
                     st[k] = st[k].float().contiguous()
         self._fast.clear()
         self._tables.clear()
+        self._dev.clear()       # (keyed on the group dicts, which super().load_state_dict has replaced)
+        self._gbuf.clear()
+        self._stepped.clear()
+        for group in self.param_groups:
+            with_state = [p for p in group["params"] if len(self.state.get(p, {}))]
+            if not with_state:
+                continue
+            dev = with_state[0].device
+            if group["capturable"]:
+                # the loaded step count goes into the group's device counter; the states view it again
+                steps = {int(self.state[p]["step"]) for p in with_state}
+                if len(steps) != 1:
+                    raise L.CfmError("libcfm Adafactor: all parameters of a group must share the step count")
+                counter = self._group_buffers(group, dev)[1]
+                counter.fill_(steps.pop())
+                self._stepped.add(id(counter))
+                for p in with_state:
+                    self.state[p]["step"] = counter
+            else:
+                for p in with_state:
+                    self.state[p]["step"] = int(self.state[p]["step"])
+            if group["scale_parameter"]:
+                # re-point RMS at the group buffer (the loaded value is overwritten by the next step anyway)
+                rms = self._group_buffers(group, dev)[0]
+                for i, p in enumerate(group["params"]):
+                    if len(self.state.get(p, {})):
+                        self.state[p]["RMS"] = rms[i]
 
     def _lr(self, group, step):
         lr = group["lr"]
@@ -94,11 +151,21 @@ class Adafactor(torch.optim.Optimizer):
         n = len(ps)
         host = (ctypes.c_char * L.size_call("cfm_adafactor_table_bytes", n))()
         row_off = col_off = blk_off = rm_off = rm_toff = cp_off = part_off = 0
+        rms, counter, _ = self._group_buffers(group, dev)
         steps = []
         for i, p in enumerate(ps):
             st = self._ensure_state(p, group)
-            st["step"] += 1
-            steps.append(st["step"])
+            if counter is not None:
+                if st["step"] is not counter:
+                    # a state that joins late (or was put there by hand) cannot share the group's device counter
+                    if torch.is_tensor(st["step"]) or st["step"] != 0 or id(counter) in self._stepped:
+                        raise L.CfmError("libcfm Adafactor: all parameters of a group must share the step count")
+                    st["step"] = counter
+            else:
+                st["step"] += 1
+                steps.append(st["step"])
+            if group["scale_parameter"]:
+                st["RMS"] = rms[i]          # the kernel writes RMS(p) of table entry i here
             factored, nb, R, C = self._geom(p)
             m = st.get("exp_avg")
             row = st["exp_avg_sq_row"] if factored else st["exp_avg_sq"]
@@ -114,7 +181,7 @@ class Adafactor(torch.optim.Optimizer):
                 rm_off += nb
                 rm_toff += lib.cfm_adafactor_rowmean_tasks(nb, R)
             blk_off += lib.cfm_adafactor_blocks(p.numel())
-        if len(set(steps)) != 1:
+        if counter is None and len(set(steps)) != 1:
             raise L.CfmError("libcfm Adafactor: all parameters of a group must share the step count")
         raw = bytes(host)
         tkey = (id(group), dev)
@@ -124,7 +191,7 @@ class Adafactor(torch.optim.Optimizer):
         else:
             table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev, non_blocking=False)
             self._tables[tkey] = (raw, table)
-        return table, steps[0], (row_off, col_off, blk_off, rm_off, rm_toff, cp_off, part_off)
+        return table, (steps[0] if steps else None), (row_off, col_off, blk_off, rm_off, rm_toff, cp_off, part_off)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -141,6 +208,7 @@ class Adafactor(torch.optim.Optimizer):
                     p.grad = p.grad.contiguous()
             n = len(ps)
             dev = ps[0].device
+            capturable = group["capturable"]
             # fast path: same parameter / gradient buffers as the cached table (every step of a
             # training loop whose gradients live in a captured graph's pool, or are re-used in
             # place): no per-parameter ctypes table build on the host, only the step counters
@@ -148,31 +216,49 @@ class Adafactor(torch.optim.Optimizer):
             fast = self._fast.get((id(group), dev))
             if fast is not None and fast[0] == ptrkey:
                 table, offs = fast[1], fast[2]
-                steps = set()
-                for p in ps:
-                    st = self.state[p]
-                    st["step"] += 1
-                    steps.add(st["step"])
-                if len(steps) != 1:
-                    raise L.CfmError("libcfm Adafactor: all parameters of a group must share the step count")
-                step = steps.pop()
+                step = None
+                if not capturable:      # (capturable: the one device counter, incremented by the step itself)
+                    steps = set()
+                    for p in ps:
+                        st = self.state[p]
+                        st["step"] += 1
+                        steps.add(st["step"])
+                    if len(steps) != 1:
+                        raise L.CfmError("libcfm Adafactor: all parameters of a group must share the step count")
+                    step = steps.pop()
                 row_off, col_off, blk_off, rm_off, rm_toff, cp_off, part_off = offs
             else:
+                if torch.cuda.is_current_stream_capturing():    # no table upload inside a capture
+                    raise L.CfmError(_NEEDS_WARMUP)
                 table, step, offs = self._build_table(group, ps, dev)
                 row_off, col_off, blk_off, rm_off, rm_toff, cp_off, part_off = offs
                 self._fast[(id(group), dev)] = (self._ptrkey(ps), table, offs)   # state now exists
             key = (id(group), dev)
             buf = self._dev.get(key)
+            scale = group["scale_parameter"]
             if (buf is None or buf[0].numel() < max(rm_off, 1) or buf[1].numel() < max(part_off, 1)
-                    or buf[2].numel() < blk_off):
+                    or buf[2].numel() < blk_off or (scale and buf[3] is None)):
                 buf = (torch.empty(max(rm_off, 1), device=dev), torch.empty(max(part_off, 1), device=dev),
-                       torch.empty(max(blk_off, 1), device=dev))
+                       torch.empty(max(blk_off, 1), device=dev),
+                       torch.empty(max(blk_off, 1), device=dev) if scale else None)     # block sums of p^2
                 self._dev[key] = buf
-            b2t = 1.0 - math.pow(step, group["decay_rate"])
             beta1 = group["beta1"] if group["beta1"] is not None else 0.0
-            L.call("cfm_adafactor_step", L.ptr(table), n, row_off, col_off, blk_off, rm_toff, cp_off, L.ptr(buf[0]),
-                   L.ptr(buf[1]), L.ptr(buf[2]),
-                   float(self._lr(group, step)), float(beta1), float(b2t), float(group["eps"][0]),
-                   float(group["clip_threshold"]), L.stream())
+            # (scale_parameter=False, weight_decay=0, not capturable: the library makes cfm_adafactor_step's launches)
+            rms, counter, scalars = self._group_buffers(group, dev)
+            h = L.AdafactorHyper(decay_rate=group["decay_rate"], beta1=beta1, eps1=group["eps"][0],
+                                 eps2=group["eps"][1], clip=group["clip_threshold"],
+                                 weight_decay=group["weight_decay"], flags=L.ADA_SCALE_PARAMETER if scale else 0)
+            if capturable:
+                h.flags |= (L.ADA_DEVICE_STEP | (L.ADA_RELATIVE_STEP if group["relative_step"] else 0)
+                            | (L.ADA_WARMUP_INIT if group["warmup_init"] else 0))
+                h.lr = group["lr"] if group["lr"] is not None else 0.0
+                h.step_dev, h.scalars_dev = L.ptr(counter), L.ptr(scalars)
+                self._stepped.add(id(counter))
+            else:
+                h.lr = self._lr(group, step)
+                h.beta2t = 1.0 - math.pow(step, group["decay_rate"])
+            L.call("cfm_adafactor_step_ex", L.ptr(table), n, row_off, col_off, blk_off, rm_toff, cp_off,
+                   L.ptr(buf[0]), L.ptr(buf[1]), L.ptr(buf[2]), L.ptr(buf[3]), L.ptr(rms), ctypes.byref(h),
+                   L.stream())
             self._keep = table      # keep the table alive until the stream has consumed it
         return loss

@@ -1,0 +1,318 @@
+"""libcfm Adafactor beyond the reference's configuration -- scale_parameter, weight_decay, the default
+constructor, capturable=True -- against transformers.Adafactor on fp64 CPU copies of the same
+parameters and gradients.  Tolerance as tests/test_gpu_optim.py: per-tensor relative L2 < 1e-5 after
+5 steps.  The capturable step computes its scalars in double on the device, as the host path does,
+so it needs no wider bound: measured on an MI355X the largest error of any case is 3.1e-7, and the
+captured replays reproduce the host-scalar runs' figures (2.58e-7; 3.02e-7 with warmup_init).  Every
+case prints the errors it measured.
+
+One list of shapes, each the smallest at which a path or boundary of the two elementwise kernels
+(ada_sumsq / ada_apply, 4096 elements per block) is taken."""
+import copy
+import ctypes
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-5
+SHAPES = [
+    (37,), (5,),            # unfactored, scalar path (numel % 4 != 0)
+    (4096,), (4097,),       # exactly one block / one block and one element
+    (64, 48),               # narrow
+    (300, 2304),            # wide, 169 blocks: the partial sums cross waves
+    (33, 3000),             # C beyond the wide limit
+    (16, 8, 3, 3),          # rows packed per lane
+    (8, 16, 1),             # C = 1
+    (2, 70, 100),           # batched
+]
+ZERO = len(SHAPES)          # (64,) zeros: RMS(p) = 0 takes the eps[1] clamp on the first step
+SMALL = len(SHAPES) + 1     # scaled by 1e-4: below the clamp throughout
+NSTEPS = 5
+
+
+@pytest.fixture(scope="module")
+def data():
+    """Initial parameters and 8 steps of gradients (fp64, CPU), made once and only read."""
+    gen = torch.Generator().manual_seed(0)
+    init = [torch.randn(s, dtype=torch.float64, generator=gen) for s in SHAPES]
+    init.append(torch.zeros(64, dtype=torch.float64))
+    init.append(torch.randn(24, 40, dtype=torch.float64, generator=gen) * 1e-4)
+    grads = [[torch.randn(p.shape, dtype=torch.float64, generator=gen) * (k + 1) for p in init] for k in range(8)]
+    return init, grads
+
+
+def _pair(data, **cfg):
+    from transformers import Adafactor as HFAdafactor
+    from nn_conformer_for_speech_recognition_amd.optim import Adafactor
+    init, _ = data
+    mine = [torch.nn.Parameter(r.float().cuda()) for r in init]
+    theirs = [torch.nn.Parameter(r.clone()) for r in init]
+    hf_cfg = {k: v for k, v in cfg.items() if k != "capturable"}
+    return mine, theirs, Adafactor(mine, **cfg), HFAdafactor(theirs, **hf_cfg)
+
+
+def _set_grads(mine, theirs, gs, inplace=True):
+    for a, b, g in zip(mine, theirs, gs):
+        if inplace and a.grad is not None:
+            a.grad.copy_(g.float())
+        else:
+            a.grad = g.float().cuda()
+        if b is not None:
+            b.grad = g.clone()
+
+
+def _errors(mine, theirs):
+    torch.cuda.synchronize()
+    return [((a.detach().double().cpu() - b.detach()).norm() / b.detach().norm()).item()
+            for a, b in zip(mine, theirs)]
+
+
+def _check(mine, theirs, what):
+    errs = _errors(mine, theirs)
+    print(what, "max rel L2", max(errs), ["%.1e" % e for e in errs])
+    for a, e in zip(mine, errs):
+        assert e < TOL, (what, tuple(a.shape), e)
+
+
+def _steps(data, mine, theirs, o1, o2, ks, inplace=True):
+    for k in ks:
+        _set_grads(mine, theirs, data[1][k], inplace)
+        o1.step()
+        o2.step()
+
+
+@pytest.mark.parametrize("inplace", [False, True])
+@pytest.mark.parametrize("beta1", [0.9, None])
+def test_scale_parameter(data, beta1, inplace):
+    """Case 1: gradients written in place (cached task table) and freshly allocated (rebuilt table)."""
+    mine, theirs, o1, o2 = _pair(data, lr=1e-2, beta1=beta1, scale_parameter=True, relative_step=False)
+    _steps(data, mine, theirs, o1, o2, range(NSTEPS), inplace)
+    _check(mine, theirs, f"scale_parameter beta1={beta1} inplace={inplace}")
+
+
+@pytest.mark.parametrize("cfg", [dict(), dict(warmup_init=True)], ids=["default", "warmup_init"])
+def test_default_constructor(data, cfg):
+    """Case 2: Adafactor(params) -- scale_parameter and relative_step, the paper's recommended mode."""
+    mine, theirs, o1, o2 = _pair(data, **cfg)
+    _steps(data, mine, theirs, o1, o2, range(NSTEPS))
+    _check(mine, theirs, f"defaults {cfg}")
+
+
+@pytest.mark.parametrize("scale", [True, False])
+def test_weight_decay(data, scale):
+    """Case 3."""
+    mine, theirs, o1, o2 = _pair(data, lr=1e-2, beta1=0.9, weight_decay=0.1, scale_parameter=scale,
+                                 relative_step=False)
+    _steps(data, mine, theirs, o1, o2, range(NSTEPS))
+    _check(mine, theirs, f"weight_decay scale_parameter={scale}")
+
+
+def test_rms_state(data):
+    """Case 4: state[p]["RMS"] is transformers' (RMS of p before the step's update), a 0-d device tensor."""
+    mine, theirs, o1, o2 = _pair(data, lr=1e-2, beta1=0.9, scale_parameter=True, relative_step=False)
+    _steps(data, mine, theirs, o1, o2, [0])
+    z = o1.state[mine[ZERO]]["RMS"]
+    assert torch.is_tensor(z) and z.is_cuda and z.dim() == 0
+    assert abs(float(z) - float(o2.state[theirs[ZERO]]["RMS"])) <= 1e-12     # both exactly 0
+    _steps(data, mine, theirs, o1, o2, range(1, NSTEPS))
+    for a, b in zip(mine, theirs):
+        got, want = float(o1.state[a]["RMS"]), float(o2.state[b]["RMS"])
+        assert want > 0 and abs(got - want) / want < TOL, (tuple(a.shape), got, want)
+    assert float(o2.state[theirs[SMALL]]["RMS"]) < 1e-3       # that tensor stayed below the eps[1] clamp
+
+
+def test_load_state_dict_then_step(data):
+    """Case 5: tests/test_gpu_optim.py's rollback with scale_parameter=True (RMS re-pointed after the load)."""
+    mine, theirs, o1, o2 = _pair(data, lr=1e-2, beta1=0.9, scale_parameter=True, relative_step=False)
+    _steps(data, mine, theirs, o1, o2, [0, 1])
+    saved, saved_hf = copy.deepcopy(o1.state_dict()), copy.deepcopy(o2.state_dict())
+    _steps(data, mine, theirs, o1, o2, [2, 3])
+    o1.load_state_dict(saved)
+    o2.load_state_dict(saved_hf)
+    _steps(data, mine, theirs, o1, o2, [4, 5])
+    _check(mine, theirs, "rollback")
+    for a, b in zip(mine, theirs):
+        got, want = float(o1.state[a]["RMS"]), float(o2.state[b]["RMS"])
+        assert abs(got - want) / want < TOL, (tuple(a.shape), got, want)
+
+
+def _all_tensors(opt, params):
+    out = [p.detach() for p in params]
+    for p in params:
+        out += [v for _, v in sorted(opt.state[p].items()) if torch.is_tensor(v)]
+    return out
+
+
+def test_neutral_step_ex_is_step(data):
+    """Case 6: cfm_adafactor_step_ex with flags 0 and weight_decay 0 computes bit for bit what
+    cfm_adafactor_step computes from the same scalars, on two clones of one optimizer's table."""
+    from nn_conformer_for_speech_recognition_amd import _lib as L
+    from nn_conformer_for_speech_recognition_amd.optim import Adafactor
+    init, grads = data
+    clones = []
+    for _ in range(2):
+        ps = [torch.nn.Parameter(r.float().cuda()) for r in init]
+        opt = Adafactor(ps, lr=1e-2, beta1=0.9, scale_parameter=False, relative_step=False)
+        _set_grads(ps, [None] * len(ps), grads[0])
+        opt.step()                                      # builds the table and the buffers
+        _set_grads(ps, [None] * len(ps), grads[1])      # in place: the table stays valid
+        clones.append((ps, opt))
+    lr, beta1, b2t, eps1, eps2, clip = 1e-2, 0.9, 1.0 - 2.0 ** -0.8, 1e-30, 1e-3, 1.0
+    for which, (ps, opt) in enumerate(clones):
+        (key, (_, table, offs)), = opt._fast.items()
+        row_off, col_off, blk_off, rm_off, rm_toff, cp_off, part_off = offs
+        rowmean, part, partial = opt._dev[key][:3]
+        common = (L.ptr(table), len(ps), row_off, col_off, blk_off, rm_toff, cp_off, L.ptr(rowmean), L.ptr(part),
+                  L.ptr(partial))
+        if which == 0:
+            L.call("cfm_adafactor_step", *common, lr, beta1, b2t, eps1, clip, L.stream())
+        else:
+            h = L.AdafactorHyper(decay_rate=-0.8, lr=lr, beta1=beta1, beta2t=b2t, eps1=eps1, eps2=eps2, clip=clip,
+                                 weight_decay=0.0, flags=0)
+            L.call("cfm_adafactor_step_ex", *common, None, None, ctypes.byref(h), L.stream())
+    torch.cuda.synchronize()
+    ta, tb = _all_tensors(clones[0][1], clones[0][0]), _all_tensors(clones[1][1], clones[1][0])
+    assert len(ta) == len(tb) and len(ta) > 3 * len(init)
+    for x, y in zip(ta, tb):
+        assert torch.equal(x, y), tuple(x.shape)
+    # and the call did step: the parameters moved
+    assert not torch.equal(ta[0], init[0].float().cuda())
+
+
+def test_step_ex_rejects_missing_buffers(data):
+    from nn_conformer_for_speech_recognition_amd import _lib as L
+    t = torch.zeros(64, device="cuda")
+    args = (L.ptr(t), 1, 0, 0, 1, 0, 0, L.ptr(t), L.ptr(t), L.ptr(t))
+    h = L.AdafactorHyper(flags=L.ADA_SCALE_PARAMETER)
+    with pytest.raises(L.CfmError, match="scale_parameter"):
+        L.call("cfm_adafactor_step_ex", *args, None, None, ctypes.byref(h), L.stream())
+    h = L.AdafactorHyper(flags=L.ADA_DEVICE_STEP)
+    with pytest.raises(L.CfmError, match="device step"):
+        L.call("cfm_adafactor_step_ex", *args, None, None, ctypes.byref(h), L.stream())
+
+
+@pytest.mark.parametrize("scale", [False, True])
+def test_rerun_is_bit_identical(data, scale):
+    """No atomics: two runs of the same steps give the same bits (scale_parameter=False is the step
+    bench.py and smoke() use; with scale_parameter the p^2 partials are summed in block order too)."""
+    from nn_conformer_for_speech_recognition_amd.optim import Adafactor
+    init, grads = data
+    runs = []
+    for _ in range(2):
+        ps = [torch.nn.Parameter(r.float().cuda()) for r in init]
+        opt = Adafactor(ps, lr=1e-2, beta1=0.9, scale_parameter=scale, relative_step=False)
+        for k in range(3):
+            _set_grads(ps, [None] * len(ps), grads[k])
+            opt.step()
+        torch.cuda.synchronize()
+        runs.append(_all_tensors(opt, ps))
+    for x, y in zip(*runs):
+        assert torch.equal(x, y), tuple(x.shape)
+
+
+CAP = dict(relative_step=True, scale_parameter=True, beta1=0.9, capturable=True)
+
+
+@pytest.mark.parametrize("warmup_init", [False, True])
+def test_capturable_graph_replay(data, warmup_init):
+    """Case 7: one eager warm-up step, step() captured once, 4 replays = 5 transformers steps; then a
+    rollback to the state saved at step 2 and one eager step.  beta2t changes every step, so a value
+    frozen at capture time would show; the relative step size is min(1e-2, 1/sqrt(step)) = 1e-2 this
+    early, so the warmup_init case (1e-6 * step) is the one where a frozen `rel` shows as well."""
+    mine, theirs, o1, o2 = _pair(data, **dict(CAP, warmup_init=warmup_init))
+    _steps(data, mine, theirs, o1, o2, [0])                 # eager warm-up: table and buffers
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        o1.step()
+    saved = saved_hf = None
+    for k in range(1, NSTEPS):
+        _set_grads(mine, theirs, data[1][k])                # into the static .grad buffers
+        g.replay()
+        o2.step()
+        if k == 1:
+            torch.cuda.synchronize()
+            saved, saved_hf = copy.deepcopy(o1.state_dict()), copy.deepcopy(o2.state_dict())
+    _check(mine, theirs, "capturable replay")
+    for p in mine:
+        st = o1.state[p]["step"]
+        assert torch.is_tensor(st) and st.is_cuda and int(st) == NSTEPS
+    assert int(saved["state"][0]["step"]) == 2
+    o1.load_state_dict(saved)
+    o2.load_state_dict(saved_hf)
+    assert int(o1.state[mine[0]]["step"]) == 2
+    _steps(data, mine, theirs, o1, o2, [5])
+    _check(mine, theirs, "capturable rollback + eager step")
+    assert int(o1.state[mine[0]]["step"]) == 3
+
+
+def test_capturable_matches_host_scalars(data):
+    """The device scalars (double pow / sqrt, rounded once) without a graph: capturable steps made eagerly,
+    with the warm-up schedule and freshly allocated gradients (the table is rebuilt around the counter)."""
+    mine, theirs, o1, o2 = _pair(data, **dict(CAP, warmup_init=True))
+    _steps(data, mine, theirs, o1, o2, range(NSTEPS), inplace=False)
+    _check(mine, theirs, "capturable eager warmup_init")
+
+
+def test_captured_graph_is_one_chain(data):
+    """The captured step is a single chain of kernel launches: no parallel branches, no copies."""
+    from nn_conformer_for_speech_recognition_amd import _lib as L
+    from nn_conformer_for_speech_recognition_amd.optim import Adafactor
+    init, grads = data
+    ps = [torch.nn.Parameter(r.float().cuda()) for r in init]
+    opt = Adafactor(ps, **CAP)
+    _set_grads(ps, [None] * len(ps), grads[0])
+    opt.step()
+    g = torch.cuda.CUDAGraph(keep_graph=True)
+    with torch.cuda.graph(g):
+        opt.step()
+    hip = L.load()          # (libcfm is linked against the HIP runtime torch uses)
+    graph = ctypes.c_void_p(g.raw_cuda_graph())
+    n = ctypes.c_size_t(0)
+    assert hip.hipGraphGetNodes(graph, None, ctypes.byref(n)) == 0
+    nodes = (ctypes.c_void_p * n.value)()
+    assert hip.hipGraphGetNodes(graph, nodes, ctypes.byref(n)) == 0
+    # scalars, column partials, rows, columns, row means, sumsq, apply
+    assert n.value == 7, n.value
+    for node in nodes:
+        kind = ctypes.c_int(-1)
+        assert hip.hipGraphNodeGetType(ctypes.c_void_p(node), ctypes.byref(kind)) == 0
+        assert kind.value == 0, kind.value                  # hipGraphNodeTypeKernel
+    ne = ctypes.c_size_t(0)
+    assert hip.hipGraphGetEdges(graph, None, None, ctypes.byref(ne)) == 0
+    src, dst = (ctypes.c_void_p * ne.value)(), (ctypes.c_void_p * ne.value)()
+    assert hip.hipGraphGetEdges(graph, src, dst, ctypes.byref(ne)) == 0
+    assert ne.value == n.value - 1
+    assert len(set(src)) == ne.value and len(set(dst)) == ne.value      # out- and in-degree <= 1: a chain
+    g.replay()
+    torch.cuda.synchronize()
+    assert int(opt.state[ps[0]]["step"]) == 2
+
+
+def test_capturable_late_parameter_raises(data):
+    """One step count per group: a parameter whose first gradient arrives after the group has stepped cannot
+    share the device counter (the host-counter path raises for it as well)."""
+    from nn_conformer_for_speech_recognition_amd import _lib as L
+    from nn_conformer_for_speech_recognition_amd.optim import Adafactor
+    init, grads = data
+    ps = [torch.nn.Parameter(r.float().cuda()) for r in init[:2]]
+    opt = Adafactor(ps, **CAP)
+    ps[0].grad = grads[0][0].float().cuda()
+    opt.step()
+    ps[1].grad = grads[0][1].float().cuda()
+    with pytest.raises(L.CfmError, match="share the step count"):
+        opt.step()
+
+
+def test_capture_without_warmup_raises(data):
+    from nn_conformer_for_speech_recognition_amd import _lib as L
+    from nn_conformer_for_speech_recognition_amd.optim import Adafactor
+    init, grads = data
+    ps = [torch.nn.Parameter(r.float().cuda()) for r in init[:2]]
+    opt = Adafactor(ps, **CAP)
+    _set_grads(ps, [None] * len(ps), grads[0][:2])
+    g = torch.cuda.CUDAGraph()
+    with pytest.raises(L.CfmError, match="one eager warm-up step builds and uploads the table and buffers"):
+        with torch.cuda.graph(g):
+            opt.step()
