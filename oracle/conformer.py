@@ -21,6 +21,20 @@ scores = ((q+u)·kᵀ + (q+v)·p[(T-1)-(i-j)]ᵀ) / sqrt(dk).
 
 Module and parameter names are torchaudio's so state dicts are interchangeable with the
 product's ``Conformer`` (and with checkpoints the reference saves, runner.py:48-77).
+
+Dropout masks can be supplied from outside (``ConformerRef(..., mask_provider=fn)`` or
+``set_mask_provider``): in train mode every dropout site then multiplies by ``fn(site, shape)``, a
+tensor of keep * scale factors, instead of drawing from torch's generator -- so the oracle can be
+run under the very masks a counter-based device dropout draws.  Sites of layer ``i`` and the shape
+of the tensor each one masks:
+
+  layers.{i}.ffn1.act / layers.{i}.ffn2.act    (B, T, ffn)   after the SiLU
+  layers.{i}.ffn1.out / layers.{i}.ffn2.out    (B, T, d)     after the second Linear
+  layers.{i}.attn.probs                        (B, H, T, T)  the softmax output
+  layers.{i}.attn.out                          (B, T, d)     self_attn_dropout
+  layers.{i}.conv.out                          (B, d, T)     channel-major, before the transpose back
+
+Without a provider nothing changes (nn.Dropout's own draw).
 """
 from __future__ import annotations
 
@@ -41,13 +55,28 @@ def rel_pos_table(T, d, dtype=torch.float32):
     return pe.to(dtype)
 
 
+class SiteDropout(nn.Dropout):
+    """nn.Dropout that asks a mask provider, when one is set, for its keep * scale factors (train mode only)."""
+
+    def __init__(self, p=0.0, site=""):
+        super().__init__(p)
+        self.site = site
+        self.provider = None
+
+    def forward(self, x):
+        if self.provider is not None and self.training:
+            return x * self.provider(self.site, tuple(x.shape)).to(x)
+        return super().forward(x)
+
+
 class FeedForwardRef(nn.Module):
     """torchaudio _FeedForwardModule (names: sequential.{0,1,4})."""
 
-    def __init__(self, d, ffn, dropout=0.0):
+    def __init__(self, d, ffn, dropout=0.0, site="ffn"):
         super().__init__()
         self.sequential = nn.Sequential(nn.LayerNorm(d), nn.Linear(d, ffn, bias=True), nn.SiLU(),
-                                        nn.Dropout(dropout), nn.Linear(ffn, d, bias=True), nn.Dropout(dropout))
+                                        SiteDropout(dropout, site + ".act"), nn.Linear(ffn, d, bias=True),
+                                        SiteDropout(dropout, site + ".out"))
 
     def forward(self, x):
         return self.sequential(x)
@@ -56,7 +85,7 @@ class FeedForwardRef(nn.Module):
 class ConvModuleRef(nn.Module):
     """torchaudio _ConvolutionModule (names: layer_norm, sequential.{0,2,3,5})."""
 
-    def __init__(self, d, K, dropout=0.0, use_group_norm=False):
+    def __init__(self, d, K, dropout=0.0, use_group_norm=False, site="conv"):
         super().__init__()
         if (K - 1) % 2 != 0:
             raise ValueError("depthwise_kernel_size must be odd to achieve 'SAME' padding.")
@@ -68,7 +97,7 @@ class ConvModuleRef(nn.Module):
             nn.GroupNorm(num_groups=1, num_channels=d) if use_group_norm else nn.BatchNorm1d(d),
             nn.SiLU(),
             nn.Conv1d(d, d, 1, stride=1, padding=0, bias=True),
-            nn.Dropout(dropout),
+            SiteDropout(dropout, site + ".out"),
         )
 
     def forward(self, x):           # x (B, T, d)
@@ -79,10 +108,12 @@ class ConvModuleRef(nn.Module):
 class RelPosMHARef(nn.Module):
     """nn.MultiheadAttention-named parameters plus linear_pos / pos_bias_u / pos_bias_v."""
 
-    def __init__(self, d, H, dropout=0.0, pos_enc="none"):
+    def __init__(self, d, H, dropout=0.0, pos_enc="none", site="attn"):
         super().__init__()
         self.d, self.H, self.dk = d, H, d // H
         self.dropout = dropout
+        self.site = site + ".probs"
+        self.provider = None
         self.pos_enc = pos_enc
         self.in_proj_weight = nn.Parameter(torch.empty(3 * d, d))
         self.in_proj_bias = nn.Parameter(torch.zeros(3 * d))
@@ -118,7 +149,9 @@ class RelPosMHARef(nn.Module):
             scores = torch.matmul(q, k.transpose(-2, -1)) / math.sqrt(dk)
         scores = scores.masked_fill(key_padding_mask[:, None, None, :], float("-inf"))
         probs = torch.softmax(scores, dim=-1)
-        if self.training and self.dropout > 0:
+        if self.training and self.provider is not None:
+            probs = probs * self.provider(self.site, tuple(probs.shape)).to(probs)
+        elif self.training and self.dropout > 0:
             probs = F.dropout(probs, self.dropout)
         o = torch.matmul(probs, v).transpose(1, 2).reshape(B, T, d)
         return self.out_proj(o)
@@ -129,14 +162,14 @@ class ConformerLayerRef(nn.Module):
     conv_module, ffn2, final_layer_norm)."""
 
     def __init__(self, d, ffn, H, K, dropout=0.0, use_group_norm=False, convolution_first=False,
-                 pos_enc="none"):
+                 pos_enc="none", site="layers.0"):
         super().__init__()
-        self.ffn1 = FeedForwardRef(d, ffn, dropout)
+        self.ffn1 = FeedForwardRef(d, ffn, dropout, site + ".ffn1")
         self.self_attn_layer_norm = nn.LayerNorm(d)
-        self.self_attn = RelPosMHARef(d, H, dropout, pos_enc)
-        self.self_attn_dropout = nn.Dropout(dropout)
-        self.conv_module = ConvModuleRef(d, K, dropout, use_group_norm)
-        self.ffn2 = FeedForwardRef(d, ffn, dropout)
+        self.self_attn = RelPosMHARef(d, H, dropout, pos_enc, site + ".attn")
+        self.self_attn_dropout = SiteDropout(dropout, site + ".attn.out")
+        self.conv_module = ConvModuleRef(d, K, dropout, use_group_norm, site + ".conv")
+        self.ffn2 = FeedForwardRef(d, ffn, dropout, site + ".ffn2")
         self.final_layer_norm = nn.LayerNorm(d)
         self.convolution_first = convolution_first
 
@@ -166,12 +199,21 @@ class ConformerRef(nn.Module):
     num_layers, depthwise_conv_kernel_size, dropout, use_group_norm, convolution_first)."""
 
     def __init__(self, input_dim, num_heads, ffn_dim, num_layers, depthwise_conv_kernel_size,
-                 dropout=0.0, use_group_norm=False, convolution_first=False, pos_enc="none"):
+                 dropout=0.0, use_group_norm=False, convolution_first=False, pos_enc="none", mask_provider=None):
         super().__init__()
         self.conformer_layers = nn.ModuleList([
             ConformerLayerRef(input_dim, ffn_dim, num_heads, depthwise_conv_kernel_size, dropout,
-                              use_group_norm, convolution_first, pos_enc)
-            for _ in range(num_layers)])
+                              use_group_norm, convolution_first, pos_enc, f"layers.{i}")
+            for i in range(num_layers)])
+        self.set_mask_provider(mask_provider)
+
+    def set_mask_provider(self, fn):
+        """fn(site_name, shape) -> keep * scale tensor of `shape` for every dropout site (module docstring), or None
+        for torch's own dropout."""
+        for m in self.modules():
+            if isinstance(m, (SiteDropout, RelPosMHARef)):
+                m.provider = fn
+        return self
 
     def forward(self, input, lengths):                # (B, T, d), (B,)
         mask = lengths_to_padding_mask(lengths, input.shape[1])

@@ -9,6 +9,7 @@ cfm_mix32 only derives the per-call key):
 import numpy as np
 import pytest
 
+from tests import dropout_hash as dh
 from tests.dropout_hash import M, attn_mix, mix32
 
 
@@ -98,3 +99,83 @@ def test_attn_mix_is_one_to_one():
     for C in (0x9E3778, 0x85EBCA):
         r = (w + (w & 0xFFFFFF) * C) & M
         assert np.unique(r.astype(np.uint32)).size == r.size
+
+
+# ------------------------------------------------------------------------------------ the mask helpers
+SEEDS = [5, (1 << 40) + 5, dh.salted(5, 3)]
+
+
+def _drop_bits_scalar(seed, idx):
+    """drop_bits of cfm_common.h, one element at a time on Python integers (no numpy: a second transcription)"""
+    def mix(x):
+        x ^= x >> 16
+        x = (x * 0x7FEB352D) & M
+        x ^= x >> 15
+        x = (x * 0x846CA68B) & M
+        return x ^ (x >> 16)
+
+    def amix(x):
+        x ^= x >> 16
+        x = (x + (x & 0xFFFFFF) * 0x9E3778) & M
+        x ^= x >> 15
+        x = (x + (x & 0xFFFFFF) * 0x85EBCA) & M
+        return x ^ (x >> 16)
+    j = idx >> 1
+    key = mix((j >> 32) ^ (seed & M) ^ mix(((seed >> 32) + 0x9E3779B9) & M))
+    h = amix(((j & M) + key) & M)
+    return h >> 16 if idx & 1 else h & 0xFFFF
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_flat_keep_matches_the_scalar_transcription_and_its_offset_is_a_shift(seed):
+    p, n = 0.1, 1003
+    full = dh.flat_keep(n, p, seed)
+    assert full.dtype == np.bool_ and full.shape == (n,)
+    thr = dh.drop_thr(p)
+    assert thr == 6554
+    for i in list(range(40)) + [n - 1]:
+        assert bool(full[i]) == (_drop_bits_scalar(seed, i) >= thr)
+    for o in (1, 3, 8):       # an odd offset moves every element to the other half of its pair hash
+        np.testing.assert_array_equal(dh.flat_keep(n - o, p, seed, offset=o), full[o:])
+    np.testing.assert_array_equal(dh.flat_keep((17, 59), p, seed), full.reshape(17, 59))
+
+
+def test_wide_and_salted_seeds_differ_from_their_low_words():
+    p, n = 0.1, 385 * 77
+    wide = (1 << 40) + 5
+    assert wide & M == 5
+    assert (dh.flat_keep(n, p, wide) != dh.flat_keep(n, p, 5)).mean() > 0.1       # independent masks: 2 p (1 - p)
+    s = dh.salted(5, 3)
+    assert s == (5 + 3 * 0x9E3779B97F4A7C15) - (1 << 64) and s >> 32 != 0         # 64-bit wrap-around, as the device
+    assert dh.salted(5, 0) == 5 and dh.salted(5, 1) == 5 + 0x9E3779B97F4A7C15
+    assert (dh.flat_keep(n, p, s) != dh.flat_keep(n, p, s & M)).mean() > 0.1
+    assert (dh.flat_keep(n, p, s) != dh.flat_keep(n, p, 5)).mean() > 0.1
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_keep_rate_is_the_thresholds(seed):
+    """385 x 77 = 29,645 elements: the keep rate within 4 binomial sigma of 1 - thr / 65536 (sigma 0.0017 at p 0.1)"""
+    p, n = 0.1, 385 * 77
+    q = 1 - dh.drop_thr(p) / 65536
+    rate = dh.gemm_keep(385, 77, p, seed).mean()
+    assert abs(rate - q) < 4 * np.sqrt(q * (1 - q) / n), rate
+    assert dh.keep_scale(p) == 65536 / (65536 - 6554) and abs(dh.keep_scale(p) - 1 / q) < 1e-12
+    assert abs(dh.keep_scale(p) - 1 / 0.9) > 1e-6          # not 1 / (1 - p): the threshold is an integer
+    assert dh.keep_scale(0.5) == 2.0
+
+
+def test_gemm_and_attention_index_conventions():
+    p, seed = 0.1, 77
+    Mr, N = 37, 77
+    flat = dh.flat_keep(3 + 2 * Mr * N, p, seed)
+    g = dh.gemm_keep(Mr, N, p, seed, offset=3, batch=2)
+    assert g.shape == (2, Mr, N)
+    np.testing.assert_array_equal(g.reshape(-1), flat[3:])               # z M N + m N + n, behind the offset
+    np.testing.assert_array_equal(dh.gemm_keep(Mr, N, p, seed), flat[:Mr * N].reshape(Mr, N))
+    B, H = 2, 2
+    for T in (6, 7):                                                      # rows of the even stride T + (T & 1)
+        Te = T + (T & 1)
+        a = dh.attn_keep(B, H, T, p, seed)
+        assert a.shape == (B, H, T, T)
+        rows = dh.flat_keep((B * H * T, Te), p, seed)
+        np.testing.assert_array_equal(a.reshape(B * H * T, T), rows[:, :T])

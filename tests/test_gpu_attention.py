@@ -25,13 +25,18 @@ def attn_mode():
     _lib.call("cfm_attn_set_mode", 0)
 
 
-def _ref(qkv, lens, B, T, H, dk, do):
+def _ref(qkv, lens, B, T, H, dk, do, keep=None, keep_scale=1.0):
+    """keep: optional (B, H, T, T) 0/1 attention-dropout mask -- probs * keep * keep_scale, as nn.MultiheadAttention
+    drops after the softmax"""
     x = qkv.float().view(B, T, 3, H, dk).requires_grad_()
     q, k, v = x[:, :, 0].transpose(1, 2), x[:, :, 1].transpose(1, 2), x[:, :, 2].transpose(1, 2)
     s = (q @ k.transpose(-1, -2)) / dk ** 0.5
     mask = torch.arange(T, device=qkv.device)[None, :] >= lens[:, None].long()
     s = s.masked_fill(mask[:, None, None, :], float("-inf"))
-    o = (s.softmax(-1) @ v).transpose(1, 2).reshape(B * T, H * dk)
+    probs = s.softmax(-1)
+    if keep is not None:
+        probs = probs * keep.to(probs) * keep_scale
+    o = (probs @ v).transpose(1, 2).reshape(B * T, H * dk)
     o.backward(do.float())
     return o.detach(), x.grad.view(B * T, 3 * H * dk)
 
@@ -116,7 +121,7 @@ def test_rowdot_epilogue_feeds_attention_bwd():
 
 
 # ------------------------------------------------------------------------------------ relative positions
-def _ref_rel(qkv, pos, pu, pv, lens, B, T, H, dk, do):
+def _ref_rel(qkv, pos, pu, pv, lens, B, T, H, dk, do, keep=None, keep_scale=1.0):
     """fp32 torch restatement of transformers' rel-pos attention core (modeling_wav2vec2_conformer.py:528-565):
     scores = ((q+u) k^T + rel_shift((q+v) p^T)) / sqrt(dk), bd[i, j] uses p row (T-1) - i + j."""
     x = qkv.float().view(B, T, 3, H, dk).requires_grad_()
@@ -131,7 +136,10 @@ def _ref_rel(qkv, pos, pu, pv, lens, B, T, H, dk, do):
     s = (ac + full.gather(-1, idx)) / dk ** 0.5
     mask = ar[None, :] >= lens[:, None].long()
     s = s.masked_fill(mask[:, None, None, :], float("-inf"))
-    o = (s.softmax(-1) @ vv).transpose(1, 2).reshape(B * T, H * dk)
+    probs = s.softmax(-1)
+    if keep is not None:           # (B, H, T, T) 0/1 attention-dropout mask, as _ref
+        probs = probs * keep.to(probs) * keep_scale
+    o = (probs @ vv).transpose(1, 2).reshape(B * T, H * dk)
     o.backward(do.float())
     return o.detach(), x.grad.view(B * T, 3 * H * dk), P.grad.view(2 * T - 1, H * dk), u.grad.reshape(-1), \
         v.grad.reshape(-1)
@@ -237,18 +245,8 @@ def test_rel_dq_from_stored_ds_matches_recompute(attn_mode, B, T, H, lens, drop_
 
 # ------------------------------------------------------------------------------------ dropout masks, read back
 def _keep(B, T, H, p, seed):
-    """numpy restatement of the attention-dropout keep mask (cfm_common.h attn_mix / drop_key, attn_common.h
-    didx): element (b, h, i, j) keeps iff the 16-bit half (j & 1) of attn_mix(((bh T + i) T2 + j/2) + key) >= thr,
-    T2 = (T rounded up to even) / 2, key = lowbias32-derived drop_key(seed, 0).  Returns (B, H, T, T) bool."""
-    key = dh.drop_key(seed)
-    thr = dh.drop_thr(p)
-    T2 = (T + (T & 1)) >> 1
-    bh = np.arange(B * H, dtype=np.uint64)[:, None, None]
-    i = np.arange(T, dtype=np.uint64)[None, :, None]
-    j = np.arange(T, dtype=np.uint64)[None, None, :]
-    hs = dh.attn_mix((((bh * T + i) * T2 + j // 2) + key) & 0xFFFFFFFF)
-    half = np.where(j % 2 == 0, hs & 0xFFFF, hs >> 16)
-    return (half >= thr).reshape(B, H, T, T)
+    """the attention-dropout keep mask (B, H, T, T) of the numpy restatement (tests/dropout_hash.py attn_keep)"""
+    return dh.attn_keep(B, H, T, p, seed)
 
 
 @pytest.mark.parametrize("mode", [0, _lib.ATTN_MODE_TILED])

@@ -1,0 +1,494 @@
+"""Every dropout site's mask, read back exactly and held against the numpy restatement of the hash
+(tests/dropout_hash.py, written from the conventions documented in cfm_common.h / attn_common.h / gemm_epilogue.h).
+
+Each case feeds a kernel inputs that make its output c * mask with a known c != 0, then asserts
+  np.array_equal(out != 0, helper_mask)        -- every element, none skipped -- and
+  kept values == c * keep_scale(p)             to the rounding of the output dtype.
+Sites: cfm_scale_dropout (8-per-thread and scalar kernels), the GEMM epilogues (generic scalar / generic 8-wide /
+every compile-time kind that carries dropout / the fp8 and MX operand kernels, under every kernel selection the
+suite forces elsewhere), the LayerNorm backward's g2 (single and pair), the attention kernels' forward
+(query-major) and dK/dV (key-major) masks past one key tile, and all of them again under a bound device step counter
+(salted_seed).
+
+Value tolerances: an fp32 output is c * fp32(keep_scale) exactly up to one rounding (rtol 2^-23); a bf16 output is that
+rounded to bf16 (rtol 2^-8); outputs through the device SiLU (v_exp_f32, v_rcp_f32: 1 ulp each, plus the argument
+scaling) get 2e-6 more; attention outputs carry the bf16 rounding of P and of the output (1e-2, as
+test_dropout_masks_read_back)."""
+import contextlib
+import ctypes
+import functools
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from nn_conformer_for_speech_recognition_amd import _lib, ops
+from tests import dropout_hash as dh
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+P = 0.1
+WIDE = (1 << 40) + 5          # a seed with a high word
+KS = float(np.float32(65536.0) / np.float32(65536 - dh.drop_thr(P)))      # drop_keep_scale, in fp32 as the device
+SILU1 = 1.0 / (1.0 + math.exp(-1.0))
+BF, F32 = torch.bfloat16, torch.float32
+RTOL = {F32: 2.0 ** -23, BF: 2.0 ** -8}
+
+
+def test_keep_scale_constant():
+    assert abs(KS - dh.keep_scale(P)) < 1e-7 * KS
+
+
+@pytest.fixture
+def gemm_mode():
+    yield lambda m: _lib.call("cfm_gemm_set_mode", m)
+    _lib.call("cfm_gemm_set_mode", _lib.GEMM_MODE_DEFAULT)
+
+
+@pytest.fixture
+def attn_mode():
+    yield lambda m: _lib.call("cfm_attn_set_mode", m)
+    _lib.call("cfm_attn_set_mode", 0)
+
+
+@contextlib.contextmanager
+def bound_counter(value):
+    """a device step counter bound for the block (cfm_rng_bind), always unbound after"""
+    ctr = torch.full((1,), value, dtype=torch.int64, device=DEV)
+    _lib.call("cfm_rng_bind", _lib.ptr(ctr))
+    try:
+        yield ctr
+    finally:
+        torch.cuda.synchronize()
+        _lib.call("cfm_rng_bind", None)
+
+
+def _check(out, mask, c, rtol, what):
+    """out: tensor of mask's shape; every element compared: zero exactly where the mask drops, c elsewhere"""
+    got = out.detach().float().cpu().numpy()
+    assert got.shape == mask.shape, (what, got.shape, mask.shape)
+    bad = (got != 0) != mask
+    assert not bad.any(), (what, "mask differs at", np.argwhere(bad)[:4].tolist(), int(bad.sum()), "of", mask.size)
+    kept = got[mask]
+    assert kept.size > 0
+    np.testing.assert_allclose(kept, np.float32(c), rtol=rtol, atol=0, err_msg=str(what))
+
+
+@functools.lru_cache(maxsize=None)
+def _gmask(M, N, seed, offset=0, batch=1):
+    return dh.gemm_keep(M, N, P, seed, offset=offset, batch=batch)
+
+
+# ------------------------------------------------------------------------------------------ cfm_scale_dropout
+@pytest.mark.parametrize("out_dtype", [F32, BF], ids=["f32", "bf16"])
+@pytest.mark.parametrize("n", [8 * 131, 1003])
+@pytest.mark.parametrize("offset", [0, 3])
+@pytest.mark.parametrize("seed", [77, WIDE])
+def test_scale_dropout_mask(n, offset, seed, out_dtype):
+    """ones * 0.5 through the 8-per-thread kernel (n % 8 == 0) and the scalar kernel; an odd offset puts every 8-group
+    on an odd base (the fifth pair hash)."""
+    x = torch.ones(n, device=DEV)
+    y = ops.scale_dropout(x, 0.5, P, seed, offset, out_dtype=out_dtype)
+    assert y.dtype == out_dtype
+    _check(y, dh.flat_keep(n, P, seed, offset), 0.5 * KS, RTOL[out_dtype], (n, offset, seed))
+
+
+# ------------------------------------------------------------------------------------------ GEMM epilogues
+def _cus():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+@contextlib.contextmanager
+def planned():
+    """collects (variant, epilogue) of every ops.gemm launch in the block: cfm_gemm_plan on the very descriptor, under
+    the current cfm_gemm_set_mode value, before it is launched"""
+    seen = []
+    cus = _cus()
+
+    def probe(kind, shape, desc, launch):
+        if kind == "gemm":
+            c = _lib.GemmChoice()
+            rc = _lib.load().cfm_gemm_plan(ctypes.byref(desc), -1, cus, ctypes.byref(c))
+            assert rc == 0, _lib.load().cfm_get_last_error()
+            seen.append((c.variant, c.epilogue))
+        return launch()
+    ops.PROBE = probe
+    try:
+        yield seen
+    finally:
+        ops.PROBE = None
+
+
+# kind -> (the compile-time epilogue it names, C dtype, residual dtype, pre dtype)
+KINDS = {
+    "f32": (_lib.GEMM_EPI_F32, F32, None, None),
+    "f32_res": (_lib.GEMM_EPI_F32_RES, F32, F32, None),
+    "bf16_res": (_lib.GEMM_EPI_BF16_RES, BF, BF, None),
+    "f32r_bf16": (_lib.GEMM_EPI_F32R_BF16, BF, F32, None),
+    "delta": (_lib.GEMM_EPI_BF16_DELTA, BF, None, None),
+    "silu": (_lib.GEMM_EPI_BF16_SILU, BF, None, BF),
+    "actg": (_lib.GEMM_EPI_BF16_ACTG, BF, None, BF),
+}
+SENTINEL = -3.0
+
+
+def _run_gemm(kind, M, N, K, seed, *, offset=0, batch=1, ldc=None, ab=BF, cdt=None, predt=None, b_kmajor=True):
+    """One launch whose output is c * mask.  Forward kinds: x = 0, bias = 1 -> out_scale * mask * keep (+ residual 0),
+    SiLU kinds silu(1) * mask * keep with the stored pre-activation exactly 1.  actg: dy = 1, w = 1, pre = 0 ->
+    K * silu'(0) * mask * keep = K/2 * mask * keep.  C is pre-filled with a sentinel, so an element no thread wrote
+    fails the mask comparison; with ldc > N the padding columns must keep it.
+    -> (out (batch, M, N) view, c, rtol, pre or None)"""
+    _, kc, rdt, kpre = KINDS[kind]
+    cdt = cdt or kc
+    predt = predt or kpre
+    ldc = ldc or N
+    C = torch.full((batch, M, ldc), SENTINEL, device=DEV, dtype=cdt)
+    kw = dict(drop_p=P, seed=seed, offset=offset, ldc=ldc)
+    if batch > 1:
+        kw.update(batch=batch, stride_a=M * K, stride_b=0, stride_c=M * ldc)
+    A = (torch.ones if kind == "actg" else torch.zeros)(batch * M, K, device=DEV, dtype=ab)
+    Bm = torch.ones((N, K) if b_kmajor else (K, N), device=DEV, dtype=ab)
+    pre = None
+    rtol = RTOL[cdt]
+    if kind == "actg":
+        pre = torch.zeros(batch, M, ldc, device=DEV, dtype=predt)
+        ops.gemm(A, Bm, C, M, N, K, b_kmajor=b_kmajor, act_grad=True, pre=pre, **kw)
+        c = K * 0.5 * KS
+    elif kind == "silu":
+        pre = torch.full((batch, M, ldc), SENTINEL, device=DEV, dtype=predt)
+        ops.gemm(A, Bm, C, M, N, K, b_kmajor=b_kmajor, bias=torch.ones(N, device=DEV), act=ops.ACT_SILU, pre=pre, **kw)
+        c = SILU1 * KS
+        rtol += 2e-6
+    else:
+        res = None if rdt is None else torch.zeros(batch, M, ldc, device=DEV, dtype=rdt)
+        ops.gemm(A, Bm, C, M, N, K, b_kmajor=b_kmajor, bias=torch.ones(N, device=DEV), out_scale=0.5, residual=res,
+                 ldr=ldc, **kw)
+        c = 0.5 * KS
+    torch.cuda.synchronize()
+    if ldc > N:
+        assert bool((C[..., N:] == SENTINEL).all()), "padding columns written"
+    if kind == "silu":
+        assert bool((pre[..., :N] == 1).all()), "stored pre-activation"
+    return C[..., :N], c, rtol, pre
+
+
+def _gemm_mask_case(kind, M, N, K, seed, want_epi=None, want_variants=None, **kw):
+    with planned() as seen:
+        out, c, rtol, _ = _run_gemm(kind, M, N, K, seed, **kw)
+    assert len(seen) == 1
+    if want_epi is not None:
+        assert seen[0][1] == want_epi, (kind, M, N, "epilogue kind", seen[0][1], "wanted", want_epi)
+    if want_variants is not None:
+        assert seen[0][0] in want_variants, (kind, M, N, "variant", seen[0][0])
+    batch, off = kw.get("batch", 1), kw.get("offset", 0)
+    mask = _gmask(M, N, seed, off, batch).reshape(batch, M, N)
+    _check(out, mask, c, rtol, (kind, M, N, K, seed, kw, seen[0]))
+    return seen[0]
+
+
+@pytest.mark.parametrize("ab", [F32, BF], ids=["f32ops", "bf16ops"])
+@pytest.mark.parametrize("M", [37, 385])
+@pytest.mark.parametrize("N,ldc", [(77, 77), (77, 80), (136, 136), (136, 144)])
+def test_gemm_generic_epilogue_masks(gemm_mode, M, N, ldc, ab):
+    """The run-time epilogue rows: N 77 is odd (rows start on odd and even bases alike, and the last 8-chunk of a row
+    is the n + 8 > N tail) and takes the per-element path; N 136 the 8-wide path (bf16 operands: forced by
+    GEMM_MODE_GENERIC_EPILOGUE -- the default would pick a compile-time kind).  ldc != N: the dropout index is the
+    element's logical position m N + n, not its address."""
+    gemm_mode(_lib.GEMM_MODE_DEFAULT | _lib.GEMM_MODE_GENERIC_EPILOGUE)
+    K = 64
+    for kind, seed in (("f32", 77), ("f32_res", WIDE), ("silu", 77), ("actg", WIDE)):
+        cdt = F32 if ab == F32 else None          # fp32 operands: fp32 C / pre (the parity mode's launches)
+        _gemm_mask_case(kind, M, N, K, seed, want_epi=_lib.GEMM_EPI_GENERIC, ldc=ldc, ab=ab, cdt=cdt,
+                        predt=F32 if ab == F32 else None)
+    _gemm_mask_case("f32_res", M, N, K, 77, want_epi=_lib.GEMM_EPI_GENERIC, ldc=ldc, ab=ab, offset=3)
+    _gemm_mask_case("f32_res", M, N, K, WIDE, want_epi=_lib.GEMM_EPI_GENERIC, ldc=ldc, ab=ab, batch=2)
+    if ab == BF and N % 8 == 0:      # MN-major B (linear_dgrad without the transposed weight copy): generic kernels
+        _gemm_mask_case("actg", M, N, K, 77, want_epi=_lib.GEMM_EPI_GENERIC, ldc=ldc, b_kmajor=False)
+
+
+@pytest.mark.parametrize("kind", list(KINDS))
+@pytest.mark.parametrize("M", [37, 385])
+@pytest.mark.parametrize("N", [512, 2048, 144])
+def test_gemm_fast_kind_masks_default_selection(kind, M, N):
+    """Every compile-time epilogue kind that carries dropout, as the default selection launches it (N 144: the
+    64 x 160 tile of Conformer-S), ragged M against every tile height; seeds with and without a high word; one odd
+    offset (drop8_fast<true>) and one batched launch (the z M N term) per kind."""
+    K = 64
+    epi = KINDS[kind][0]
+    _gemm_mask_case(kind, M, N, K, 77 if M == 37 else WIDE, want_epi=epi)
+    if N == 512:
+        _gemm_mask_case(kind, M, N, K, WIDE, want_epi=epi, offset=3)
+        _gemm_mask_case(kind, M, N, K, 77, want_epi=epi, batch=2)
+
+
+def _forced(sel):
+    return _lib.GEMM_MODE_PIPE | sel << _lib.GEMM_MODE_SEL_SHIFT
+
+
+_D = _lib.GEMM_MODE_DEFAULT
+_STAGED = (_lib.GEMM_V_STAGED_BF16_128, _lib.GEMM_V_STAGED_BF16_256)
+# (id, cfm_gemm_set_mode value, the variants it must launch at M 385 / N 512, whether that variant carries the kinds)
+MODES = [
+    ("staged256", _lib.GEMM_MODE_STAGED256, _STAGED, False),
+    ("pipe", _lib.GEMM_MODE_PIPE, (_lib.GEMM_V_PIPE256S,), True),
+    ("pipe256", _forced(_lib.GEMM_SEL_PIPE256), (_lib.GEMM_V_PIPE256,), False),
+    ("pipe256s", _forced(_lib.GEMM_SEL_PIPE256S), (_lib.GEMM_V_PIPE256S,), True),
+    ("ws96", _forced(_lib.GEMM_SEL_192), (_lib.GEMM_V_WS96,), True),
+    ("ws192", _forced(_lib.GEMM_SEL_192) | _lib.GEMM_MODE_KEEP_WS192, (_lib.GEMM_V_WS192,), True),
+    ("pipe192", _forced(_lib.GEMM_SEL_192) | _lib.GEMM_MODE_KEEP_SHARED_DMA, (_lib.GEMM_V_PIPE192,), False),
+    ("pipe192s8", _forced(_lib.GEMM_SEL_PIPE192S8), (_lib.GEMM_V_PIPE192S8,), True),
+    ("keep_shared_dma", _D | _lib.GEMM_MODE_KEEP_SHARED_DMA, (_lib.GEMM_V_PIPE256S,), True),
+    ("keep_pipe192", _D | _lib.GEMM_MODE_KEEP_PIPE192, (_lib.GEMM_V_PIPE256S,), True),
+    ("keep_ws192", _D | _lib.GEMM_MODE_KEEP_WS192, (_lib.GEMM_V_PIPE256S,), True),
+    ("generic_epilogue", _D | _lib.GEMM_MODE_GENERIC_EPILOGUE, (_lib.GEMM_V_PIPE256S,), False),
+    ("generic_dropout", _D | _lib.GEMM_MODE_GENERIC_DROPOUT, (_lib.GEMM_V_PIPE256S,), False),
+]
+
+
+@pytest.mark.parametrize("name,mode,variants,fast", MODES, ids=[m[0] for m in MODES])
+def test_gemm_masks_under_every_kernel_selection(gemm_mode, name, mode, variants, fast):
+    """The same masks from every kernel variant and both epilogue forms: each cfm_gemm_set_mode value and forced
+    selector the suite uses elsewhere, at M 385 (ragged against 96 / 192 / 256-row tiles), N 512, K 64; the launch is
+    asserted to be the variant and the epilogue kind the mode stands for.  (GENERIC_DROPOUT: the generic rows with
+    dropout_scale8 in place of the hoisted key.)"""
+    gemm_mode(mode)
+    for i, kind in enumerate(KINDS):
+        epi = KINDS[kind][0] if fast else _lib.GEMM_EPI_GENERIC
+        _gemm_mask_case(kind, 385, 512, 64, (77, WIDE)[i & 1], want_epi=epi, want_variants=variants, offset=3 * (i & 1))
+    _gemm_mask_case("f32_res", 37, 2048, 64, 77, want_epi=KINDS["f32_res"][0] if fast else _lib.GEMM_EPI_GENERIC, batch=2)
+
+
+def test_linear_and_linear_dgrad_wrappers_carry_seed_and_offset():
+    """ops.linear / ops.linear_dgrad (what conformer.py calls) hand seed and offset through unchanged."""
+    M, d, ffn = 37, 512, 2048
+    x = torch.zeros(M, d, device=DEV, dtype=BF)
+    w1 = torch.ones(ffn, d, device=DEV, dtype=BF)
+    pre = torch.empty(M, ffn, device=DEV, dtype=BF)
+    with planned() as seen:
+        h = ops.linear(x, w1, torch.ones(ffn, device=DEV), act=ops.ACT_SILU, pre=pre, drop_p=P, seed=WIDE, offset=3)
+        dy = torch.ones(M, d, device=DEV, dtype=BF)
+        da = ops.linear_dgrad(dy, torch.ones(d, ffn, device=DEV, dtype=BF), pre=torch.zeros_like(pre), act_grad=True,
+                              drop_p=P, seed=WIDE, offset=3, wt=torch.ones(ffn, d, device=DEV, dtype=BF))
+    torch.cuda.synchronize()
+    assert [s[1] for s in seen] == [_lib.GEMM_EPI_BF16_SILU, _lib.GEMM_EPI_BF16_ACTG]
+    assert bool((pre == 1).all())
+    mask = _gmask(M, ffn, WIDE, 3)
+    _check(h, mask, SILU1 * KS, RTOL[BF] + 2e-6, "linear silu")
+    _check(da, mask, d * 0.5 * KS, RTOL[BF], "linear_dgrad act_grad")
+
+
+@pytest.mark.parametrize("M,N", [(37, 512), (385, 2048), (385, 512)])
+def test_fp8_and_mx_gemm_silu_dropout_masks(M, N):
+    """The fp8 operand GEMMs with the FFN-up epilogue (bias + SiLU + bf16 pre + dropout): per-tensor scales (generic
+    epilogue rows), MX block scales (EF_BF16_SILU), and MX with the MX copy of the output (EF_BF16_SILU_MX), whose
+    dequantised copy must show the same mask."""
+    K = 128
+    xq = torch.zeros(M, K, device=DEV, dtype=torch.float8_e4m3fn)
+    one = torch.ones(1, device=DEV)
+    w = torch.ones(N, K, device=DEV, dtype=BF)
+    wq, sw = ops.quant_fp8(w)
+    wmq, wms = ops.quant_mx(w)
+    xms = torch.full((M, K // 32), 127, device=DEV, dtype=torch.uint8)       # e8m0 2^0
+    b = torch.ones(N, device=DEV)
+    c, rtol = SILU1 * KS, RTOL[BF] + 2e-6
+    want = [_lib.GEMM_EPI_GENERIC, _lib.GEMM_EPI_BF16_SILU, _lib.GEMM_EPI_BF16_SILU_MX]
+    with planned() as seen:
+        pre0 = torch.full((M, N), SENTINEL, device=DEV, dtype=BF)
+        y0 = ops.linear(xq, wq, b, act=ops.ACT_SILU, pre=pre0, drop_p=P, seed=77, x_scale=one, w_scale=sw)
+        pre1 = torch.full((M, N), SENTINEL, device=DEV, dtype=BF)
+        y1 = ops.linear(xq, wmq, b, act=ops.ACT_SILU, pre=pre1, drop_p=P, seed=WIDE, x_mx=xms, w_mx=wms)
+        pre2 = torch.full((M, N), SENTINEL, device=DEV, dtype=BF)
+        y8 = torch.empty(M, N, device=DEV, dtype=torch.float8_e4m3fn)
+        s8 = torch.empty(M, N // 32, device=DEV, dtype=torch.uint8)
+        y2 = ops.linear(xq, wmq, b, act=ops.ACT_SILU, pre=pre2, drop_p=P, seed=WIDE, offset=3, x_mx=xms, w_mx=wms,
+                        mx_out=(y8, s8))
+    torch.cuda.synchronize()
+    assert [s[1] for s in seen] == want, seen
+    for pre in (pre0, pre1, pre2):
+        assert bool((pre == 1).all())
+    _check(y0, _gmask(M, N, 77), c, rtol, "fp8 per-tensor")
+    _check(y1, _gmask(M, N, WIDE), c, rtol, "mx")
+    _check(y2, _gmask(M, N, WIDE, 3), c, rtol, "mx + mx_out")
+    _check(ops.dequant_mx(y8, s8), _gmask(M, N, WIDE, 3), c, 2.0 ** -3, "mx copy")     # e4m3: 3 mantissa bits
+
+
+# ------------------------------------------------------------------------------------------ LayerNorm backward g2
+@functools.lru_cache(maxsize=None)
+def _ln_case(D, M=37):
+    g = torch.Generator().manual_seed(D)
+    x = (torch.randn(M, D, generator=g) * 2 + 0.3).to(DEV)
+    g1, b1 = (torch.rand(D, generator=g) + 0.5).to(DEV), torch.randn(D, generator=g).to(DEV)
+    g2, b2 = (torch.rand(D, generator=g) + 0.5).to(DEV), torch.randn(D, generator=g).to(DEV)
+    dy = torch.randn(M, D, generator=g).to(DEV, BF)
+    dres = torch.randn(M, D, generator=g).to(DEV)
+    dres[3, :5] = 0
+    return x, g1, b1, g2, b2, dy, dres
+
+
+def _check_g2(g2, dx, seed, dtype, what):
+    """g2 == scale * keep * mask o dx from the returned dx: compared as VALUES everywhere (a dx element that is exactly
+    0 gives 0 whatever the mask says), and as a zero pattern wherever dx != 0"""
+    M, D = dx.shape
+    mask = dh.flat_keep((M, D), P, seed)
+    dxn = dx.float().cpu().numpy()
+    want = np.float32(0.5) * np.float32(KS) * dxn * mask
+    got = g2.float().cpu().numpy()
+    assert g2.dtype == dtype
+    np.testing.assert_array_equal((got != 0), mask & (dxn != 0), err_msg=str(what))
+    np.testing.assert_allclose(got, want, rtol=2 * RTOL[dtype], atol=0, err_msg=str(what))
+
+
+@pytest.mark.parametrize("dtype", [BF, F32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("D", [144, 512, 100])
+@pytest.mark.parametrize("seed", [77, WIDE])
+def test_layernorm_bwd_g2_mask(D, seed, dtype):
+    """cfm_layernorm_bwd_drop's g2 (bf16: from the same kernel for D 512 / 144, the separate pass for D 100; fp32: always
+    the separate cfm_scale_dropout) against 0.5 * keep * mask o dx."""
+    x, g1, b1, _, _, dy, dres = _ln_case(D)
+    _, mu, rs = ops.layernorm_fwd(x, g1, b1, out_dtype=BF)
+    dx, _, _, g2 = ops.layernorm_bwd(dy, x, g1, mu, rs, dres=dres, drop=(0.5, P, seed, dtype))
+    torch.cuda.synchronize()
+    _check_g2(g2, dx, seed, dtype, (D, seed))
+    dx0 = torch.zeros_like(dx)      # and with gradients that are exactly zero: zeros whatever the mask says
+    z = ops.layernorm_bwd(torch.zeros_like(dy), x, g1, mu, rs, dres=dx0, drop=(0.5, P, seed, dtype))
+    assert bool((z[0] == 0).all()) and bool((z[3] == 0).all())
+
+
+@pytest.mark.parametrize("dtype", [BF, F32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("D", [144, 512])
+@pytest.mark.parametrize("seed", [77, WIDE])
+def test_layernorm_bwd_pair_g2_mask(D, seed, dtype):
+    """cfm_layernorm_bwd_pair's g2 (the fused pair exists for D 144 / 512; D 100 is refused by the kernel:
+    test_pair_refuses_unsupported_width)."""
+    x, g1, b1, g2w, b2, dz, dres = _ln_case(D)
+    _, _, m1, r1, m2, r2 = ops.layernorm_fwd_pair(x, g1, b1, g2w, b2, out_dtype=BF)
+    dx, _, _, g2 = ops.layernorm_bwd_pair(dz, dres, x, g1, b1, m1, r1, g2w, m2, r2, drop=(0.5, P, seed, dtype))
+    torch.cuda.synchronize()
+    _check_g2(g2, dx, seed, dtype, (D, seed))
+
+
+# ------------------------------------------------------------------------------------------ attention
+ATTN_CASES = [(130, 64, [130, 65]), (97, 64, [97, 97]), (70, 36, [70, 70])]
+
+
+@functools.lru_cache(maxsize=None)
+def _amask(B, H, T, seed):
+    return dh.attn_keep(B, H, T, P, seed)
+
+
+def _attn_masks_read_back(T, dk, lens, seed, rel, dtype=BF):
+    """q = k = 0 (rel: pos = u = v = 0 too) makes P uniform over the valid keys, 1 / len.  Pass r puts the identity into
+    the rows of block r: V[j] = e_(j - r dk) makes o[i, c] = keep(i, r dk + c) / len * keep_scale, and dO[i] =
+    e_(i - r dk) makes dV[j, c] = keep(r dk + c, j) / len * keep_scale -- block r of the query-major forward mask and
+    of the key-major dK/dV mask.  -> (fwd (B, H, T, T) values, bwd (B, H, T, T) values) assembled over the passes."""
+    B, H = 2, 2
+    ln = torch.tensor(lens, dtype=torch.int32, device=DEV)
+    fwd = torch.zeros(B, H, T, T)
+    bwd = torch.zeros(B, H, T, T)
+    pos = pu = pv = None
+    if rel:
+        pos = torch.zeros(2 * T - 1, H * dk, device=DEV, dtype=dtype)
+        pu = torch.zeros(H * dk, device=DEV)
+        pv = torch.zeros(H * dk, device=DEV)
+    for r in range((T + dk - 1) // dk):
+        n = min(dk, T - r * dk)
+        eye = torch.zeros(T, dk)
+        eye[r * dk:r * dk + n, :n] = torch.eye(n)
+        qkv = torch.zeros(B, T, 3, H, dk)
+        qkv[:, :, 2] = eye[None, :, None, :]
+        qkv = qkv.reshape(B * T, 3 * H * dk).to(DEV, dtype)
+        do = eye[None, :, None, :].expand(B, T, H, dk).reshape(B * T, H * dk).to(DEV, dtype).contiguous()
+        o, lse = ops.attn_fwd(qkv, ln, B, T, H, dk, pos, pu, pv, drop_p=P, seed=seed)
+        dqkv = ops.attn_bwd(qkv, o, do, lse, ln, B, T, H, dk, pos, pu, pv, drop_p=P, seed=seed)[0]
+        torch.cuda.synchronize()
+        fwd[:, :, :, r * dk:r * dk + n] = o.float().view(B, T, H, dk)[..., :n].permute(0, 2, 1, 3).cpu()
+        dv = dqkv.float().view(B, T, 3, H, dk)[:, :, 2, :, :n]                          # (B, j, H, c) = (b, h, i = c, j)
+        bwd[:, :, r * dk:r * dk + n, :] = dv.permute(0, 2, 3, 1).cpu()
+    return fwd.numpy(), bwd.numpy()
+
+
+def _check_attn(T, dk, lens, seed, rel, mask_seed=None, dtype=BF):
+    fwd, bwd = _attn_masks_read_back(T, dk, lens, seed, rel, dtype)
+    keep = _amask(2, 2, T, seed if mask_seed is None else mask_seed)
+    for b, n in enumerate(lens):
+        want = keep[b, :, :n, :].copy()
+        want[:, :, n:] = False                                   # keys at or past len contribute nothing
+        for name, got in (("fwd", fwd[b, :, :n, :]), ("dV", bwd[b, :, :n, :])):     # (rows of padded queries: not compared)
+            bad = (got > 0) != want
+            assert not bad.any(), (name, T, dk, b, n, seed, rel, np.argwhere(bad)[:4].tolist(), int(bad.sum()))
+            assert (got >= 0).all()
+            np.testing.assert_allclose(got[want], KS / n, rtol=1e-2, err_msg=f"{name} b{b}")
+
+
+@pytest.mark.parametrize("mode", [0, _lib.ATTN_MODE_TILED, _lib.ATTN_MODE_DQ_RECOMPUTE, _lib.ATTN_MODE_REL_ZERO_FILL],
+                         ids=["whole", "tiled", "dqrc", "whole_qs1"])
+@pytest.mark.parametrize("T,dk,lens", ATTN_CASES)
+@pytest.mark.parametrize("seed", [9, WIDE])
+def test_attention_masks_past_one_key_tile(attn_mode, mode, T, dk, lens, seed):
+    """Three key tiles with a ragged second utterance (kt * TILE enters didx); odd T (the T_even row stride); dk 36.
+    The whole-head kernels split these B H = 4 heads over 3-4 workgroups each (head_split); ATTN_MODE_REL_ZERO_FILL
+    keeps one workgroup per head, the split a full-size batch gets."""
+    attn_mode(mode)
+    _check_attn(T, dk, lens, seed, rel=False)
+
+
+@pytest.mark.parametrize("mode", [0, _lib.ATTN_MODE_REL_SIMT, _lib.ATTN_MODE_REL_DQ_RECOMPUTE,
+                                  _lib.ATTN_MODE_REL_ZERO_FILL], ids=["mfma", "simt", "dqrc", "mfma_qs1"])
+@pytest.mark.parametrize("T,dk,lens", ATTN_CASES)
+@pytest.mark.parametrize("seed", [9, WIDE])
+def test_rel_attention_masks_past_one_key_tile(attn_mode, mode, T, dk, lens, seed):
+    attn_mode(mode)
+    _check_attn(T, dk, lens, seed, rel=True)
+
+
+@pytest.mark.parametrize("rel", [False, True], ids=["abs", "rel"])
+def test_fp32_attention_masks(rel):
+    """fp32 q / k / v (the parity mode's attention: the SIMT kernels of attention_simt.hip)."""
+    _check_attn(97, 64, [97, 40], 9, rel=rel, dtype=F32)
+
+
+# ------------------------------------------------------------------------------------------ the device step counter
+def test_salted_masks_every_family(gemm_mode, attn_mode):
+    """A bound device counter of value 3: every family draws the mask of salted(seed, 3) -- and not the unsalted one
+    (the helper's two masks differ on ~18 % of the elements, so passing one excludes the other)."""
+    ctr = 3
+    with bound_counter(ctr):
+        for seed in (77, WIDE):
+            s = dh.salted(seed, ctr)
+            y = ops.scale_dropout(torch.ones(1003, device=DEV), 0.5, P, seed, 3)
+            _check(y, dh.flat_keep(1003, P, s, 3), 0.5 * KS, RTOL[F32], "scale_dropout scalar")
+            y = ops.scale_dropout(torch.ones(8 * 131, device=DEV), 0.5, P, seed, 3, out_dtype=BF)
+            _check(y, dh.flat_keep(8 * 131, P, s, 3), 0.5 * KS, RTOL[BF], "scale_dropout x8")
+            for kind, N, epi in (("f32_res", 77, _lib.GEMM_EPI_GENERIC), ("f32_res", 512, _lib.GEMM_EPI_F32_RES),
+                                 ("silu", 512, _lib.GEMM_EPI_BF16_SILU), ("actg", 512, _lib.GEMM_EPI_BF16_ACTG),
+                                 ("delta", 144, _lib.GEMM_EPI_BF16_DELTA)):
+                with planned() as seen:
+                    out, c, rtol, _ = _run_gemm(kind, 37, N, 64, seed, offset=3)
+                assert seen[0][1] == epi
+                _check(out[0], dh.gemm_keep(37, N, P, s, offset=3), c, rtol, ("salted", kind, N))
+            gemm_mode(_lib.GEMM_MODE_STAGED256)
+            out, c, rtol, _ = _run_gemm("f32_res", 37, 136, 64, seed)
+            _check(out[0], dh.gemm_keep(37, 136, P, s), c, rtol, "salted staged")
+            gemm_mode(_lib.GEMM_MODE_DEFAULT)
+            for D in (144, 512, 100):
+                x, g1, b1, g2w, b2, dy, dres = _ln_case(D)
+                _, mu, rs = ops.layernorm_fwd(x, g1, b1, out_dtype=BF)
+                dx, _, _, g2 = ops.layernorm_bwd(dy, x, g1, mu, rs, dres=dres, drop=(0.5, P, seed, BF))
+                _check_g2(g2, dx, s, BF, ("salted ln", D))
+                if D != 100:
+                    _, _, m1, r1, m2, r2 = ops.layernorm_fwd_pair(x, g1, b1, g2w, b2, out_dtype=BF)
+                    dx, _, _, g2 = ops.layernorm_bwd_pair(dy, dres, x, g1, b1, m1, r1, g2w, m2, r2,
+                                                          drop=(0.5, P, seed, BF))
+                    _check_g2(g2, dx, s, BF, ("salted ln pair", D))
+        for mode in (0, _lib.ATTN_MODE_TILED, _lib.ATTN_MODE_DQ_RECOMPUTE):
+            attn_mode(mode)
+            _check_attn(97, 64, [97, 60], 9, rel=False, mask_seed=dh.salted(9, ctr))
+        for mode in (0, _lib.ATTN_MODE_REL_SIMT, _lib.ATTN_MODE_REL_DQ_RECOMPUTE):
+            attn_mode(mode)
+            _check_attn(97, 64, [97, 60], 9, rel=True, mask_seed=dh.salted(9, ctr))
+        attn_mode(0)
+        _check_attn(70, 36, [70, 33], WIDE, rel=False, mask_seed=dh.salted(WIDE, ctr), dtype=F32)
+    # unbound again: the plain seed's mask
+    y = ops.scale_dropout(torch.ones(1003, device=DEV), 0.5, P, 77, 0)
+    _check(y, dh.flat_keep(1003, P, 77), 0.5 * KS, RTOL[F32], "unbound")
