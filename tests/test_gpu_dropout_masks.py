@@ -15,7 +15,6 @@ rounded to bf16 (rtol 2^-8); outputs through the device SiLU (v_exp_f32, v_rcp_f
 scaling) get 2e-6 more; attention outputs carry the bf16 rounding of P and of the output (1e-2, as
 test_dropout_masks_read_back)."""
 import contextlib
-import ctypes
 import functools
 import math
 
@@ -25,6 +24,8 @@ import torch
 
 from nn_conformer_for_speech_recognition_amd import _lib, ops
 from tests import dropout_hash as dh
+from tests import gemm_exact
+from tests.gemm_exact import planned        # (variant, epilogue) of every ops.gemm launch in a block
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -42,8 +43,7 @@ def test_keep_scale_constant():
 
 @pytest.fixture
 def gemm_mode():
-    yield lambda m: _lib.call("cfm_gemm_set_mode", m)
-    _lib.call("cfm_gemm_set_mode", _lib.GEMM_MODE_DEFAULT)
+    yield from gemm_exact.gemm_mode_fixture()
 
 
 @pytest.fixture
@@ -95,31 +95,6 @@ def test_scale_dropout_mask(n, offset, seed, out_dtype):
 
 
 # ------------------------------------------------------------------------------------------ GEMM epilogues
-def _cus():
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-@contextlib.contextmanager
-def planned():
-    """collects (variant, epilogue) of every ops.gemm launch in the block: cfm_gemm_plan on the very descriptor, under
-    the current cfm_gemm_set_mode value, before it is launched"""
-    seen = []
-    cus = _cus()
-
-    def probe(kind, shape, desc, launch):
-        if kind == "gemm":
-            c = _lib.GemmChoice()
-            rc = _lib.load().cfm_gemm_plan(ctypes.byref(desc), -1, cus, ctypes.byref(c))
-            assert rc == 0, _lib.load().cfm_get_last_error()
-            seen.append((c.variant, c.epilogue))
-        return launch()
-    ops.PROBE = probe
-    try:
-        yield seen
-    finally:
-        ops.PROBE = None
-
-
 # kind -> (the compile-time epilogue it names, C dtype, residual dtype, pre dtype)
 KINDS = {
     "f32": (_lib.GEMM_EPI_F32, F32, None, None),
@@ -222,22 +197,20 @@ def test_gemm_fast_kind_masks_default_selection(kind, M, N):
         _gemm_mask_case(kind, M, N, K, 77, want_epi=epi, batch=2)
 
 
-def _forced(sel):
-    return _lib.GEMM_MODE_PIPE | sel << _lib.GEMM_MODE_SEL_SHIFT
-
+_M = gemm_exact.MODES        # the forced selections, shared with the exact GEMM tests
 
 _D = _lib.GEMM_MODE_DEFAULT
 _STAGED = (_lib.GEMM_V_STAGED_BF16_128, _lib.GEMM_V_STAGED_BF16_256)
 # (id, cfm_gemm_set_mode value, the variants it must launch at M 385 / N 512, whether that variant carries the kinds)
 MODES = [
-    ("staged256", _lib.GEMM_MODE_STAGED256, _STAGED, False),
+    ("staged256", _M["staged"], _STAGED, False),
     ("pipe", _lib.GEMM_MODE_PIPE, (_lib.GEMM_V_PIPE256S,), True),
-    ("pipe256", _forced(_lib.GEMM_SEL_PIPE256), (_lib.GEMM_V_PIPE256,), False),
-    ("pipe256s", _forced(_lib.GEMM_SEL_PIPE256S), (_lib.GEMM_V_PIPE256S,), True),
-    ("ws96", _forced(_lib.GEMM_SEL_192), (_lib.GEMM_V_WS96,), True),
-    ("ws192", _forced(_lib.GEMM_SEL_192) | _lib.GEMM_MODE_KEEP_WS192, (_lib.GEMM_V_WS192,), True),
-    ("pipe192", _forced(_lib.GEMM_SEL_192) | _lib.GEMM_MODE_KEEP_SHARED_DMA, (_lib.GEMM_V_PIPE192,), False),
-    ("pipe192s8", _forced(_lib.GEMM_SEL_PIPE192S8), (_lib.GEMM_V_PIPE192S8,), True),
+    ("pipe256", _M["pipe256"], (_lib.GEMM_V_PIPE256,), False),
+    ("pipe256s", _M["pipe256s"], (_lib.GEMM_V_PIPE256S,), True),
+    ("ws96", _M["ws96"], (_lib.GEMM_V_WS96,), True),
+    ("ws192", _M["ws192"], (_lib.GEMM_V_WS192,), True),
+    ("pipe192", _M["pipe192"], (_lib.GEMM_V_PIPE192,), False),
+    ("pipe192s8", _M["pipe192s8"], (_lib.GEMM_V_PIPE192S8,), True),
     ("keep_shared_dma", _D | _lib.GEMM_MODE_KEEP_SHARED_DMA, (_lib.GEMM_V_PIPE256S,), True),
     ("keep_pipe192", _D | _lib.GEMM_MODE_KEEP_PIPE192, (_lib.GEMM_V_PIPE256S,), True),
     ("keep_ws192", _D | _lib.GEMM_MODE_KEEP_WS192, (_lib.GEMM_V_PIPE256S,), True),
