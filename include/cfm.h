@@ -733,6 +733,24 @@ int cfm_ctc_greedy_decode(const float* logits, long sb, long st, const int32_t* 
                           int V, int blank, int pad, int collapse, int64_t* ids, int32_t* out,
                           int32_t* out_len, void* stream);
 
+/* CTC prefix beam search without a language model: the alternative to the argmax decode of ASRNN.predict
+ * (asrnn.py:48-58) and of the Runner's metric and pseudo-label passes (runner.py:150,220,275), which follow one
+ * alignment; the beam sums the alignments of each label prefix.  The surface is modelled on torchaudio's CUDA CTC
+ * decoder.  logits fp32, row (b, t) at b*sb + t*st (logits or log-probabilities: log-softmax is applied); lens int32
+ * on the device (nullable, clamped to [0, T], never read back); 1 <= nbest <= beam <= 128, 2 <= V <= 16384,
+ * 0 <= blank < V, pad in [0, V) or < 0 for none (never emitted).  The `beam` prefixes of highest p_b (+) p_nb survive
+ * each frame, in descending order; the first nbest after lens[b] frames are the hypotheses:
+ *   tokens (B, nbest, T) int32 padded with -1, out_len (B, nbest), score (B, nbest) = log p_b (+) p_nb (natural log);
+ *   lens[b] == 0: one empty hypothesis of score 0; missing hypotheses: length 0, score -inf.
+ * bp_parent / bp_token (B, T, beam) int32, caller-allocated: slot s of frame t came from slot bp_parent of frame
+ * t - 1 (frame 0: slot 0, the empty prefix) by appending bp_token (-1: prefix unchanged); bp_parent == -1: empty
+ * slot; slots in descending score order; frames t >= lens[b] unspecified.  ws: cfm_ctc_beam_ws_bytes(B, T, beam).
+ * Three launches, no host synchronisation (graph-capturable); results are bit-identical from run to run. */
+size_t cfm_ctc_beam_ws_bytes(int B, int T, int W);
+int cfm_ctc_beam_decode(const float* logits, long sb, long st, const int32_t* lens, int B, int T, int V,
+                        int blank, int pad, int beam, int nbest, int32_t* bp_parent, int32_t* bp_token,
+                        int32_t* tokens, int32_t* out_len, float* score, void* ws, void* stream);
+
 /* BiLSTM decoder recurrence: replaces the cuDNN/MIOpen recurrence of the
  * reference's nn.LSTM (asrnn.py:38 construct, :252 call on the 2-D encoder output = ONE unbatched
  * sequence of L = B*T_enc steps).  Gate order i, f, g, o (torch).  One cooperative launch per pass;

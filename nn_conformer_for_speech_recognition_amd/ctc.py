@@ -10,6 +10,8 @@
                        logits gradient in the compute dtype straight into the head's two GEMMs).
   greedy_decode        ASRNN.predict (asrnn.py:48-58, argmax) + the id filter of Vocab.decode
                        (myvocab.py:211-231: <pad>/<blank> dropped, no repeat collapse by default).
+  beam_search_decode   CTC prefix beam search without a language model: the alternative to that argmax
+                       (modelled on torchaudio's CUDA CTC decoder).
 
 Everything is stream-ordered with no host synchronisation when targets are padded (B, S) and the
 lengths are device tensors, so a whole training step can be captured into one HIP graph.
@@ -183,3 +185,33 @@ def greedy_decode(logits, lengths=None, blank=0, pad=-1, collapse=False, batch_f
     B = x.shape[0] if batch_first else x.shape[1]
     ln = None if lengths is None else _lengths(lengths, B, x.device)
     return ops.ctc_greedy_decode(x, ln, blank, pad, collapse, batch_first, compact)
+
+
+BEAM_MAX = 128
+
+
+def beam_search_decode(logits, lengths=None, beam_size=16, blank=0, pad=-1, nbest=1, batch_first=True,
+                       return_trace=False):
+    """CTC prefix beam search on the device (cfm_ctc_beam_decode; no language model).
+    Returns (tokens (B, nbest, T) int32 padded with -1, lens (B, nbest) int32, scores (B, nbest) fp32 = log of
+    the summed alignment probability the beam kept for each hypothesis), best first; with return_trace also
+    (bp_parent, bp_token) (B, T, beam_size) int32, the back-pointer table.  `pad` (< 0: none) is never emitted."""
+    if not isinstance(beam_size, int) or isinstance(beam_size, bool) or not 1 <= beam_size <= BEAM_MAX:
+        raise ValueError(f"beam_size must be an integer in [1, {BEAM_MAX}], got {beam_size!r}")
+    if not isinstance(nbest, int) or isinstance(nbest, bool) or not 1 <= nbest <= beam_size:
+        raise ValueError(f"nbest must be an integer in [1, beam_size], got {nbest!r}")
+    if not logits.is_cuda or logits.dtype != torch.float32:
+        raise RuntimeError("beam_search_decode runs on libcfm: fp32 CUDA logits required")
+    if logits.dim() != 3:
+        raise ValueError("logits must be (B, T, V), or (T, B, V) with batch_first=False")
+    V = logits.shape[-1]
+    _check_blank(blank, V)
+    if pad >= V:
+        raise ValueError(f"pad must be in label range [0, {V}) or negative, got {pad}")
+    x = logits if logits.stride(-1) == 1 else logits.contiguous()
+    B = x.shape[0] if batch_first else x.shape[1]
+    ln = None if lengths is None else _lengths(lengths, B, x.device)
+    tokens, lens, scores, bp_parent, bp_token = ops.ctc_beam_decode(x, ln, beam_size, blank, pad, nbest, batch_first)
+    if return_trace:
+        return tokens, lens, scores, (bp_parent, bp_token)
+    return tokens, lens, scores

@@ -13,6 +13,8 @@ MI355X build (documented in DESIGN.md):
                                            statistics, no cross-replica reduce); default False
   specaug_ref_noop_masks bool              reproduce the reference's no-op masks (asrnn.py:141,165)
   dp_world_size          int               set by the data-parallel launcher
+  beam_size              int               0: the reference's argmax decode; > 0: the Runner's metric and pseudo-label
+                                           passes decode with a CTC prefix beam search of that width (set_beam_size)
 """
 from __future__ import annotations
 
@@ -57,7 +59,7 @@ _NST_LM = dict(nst=True, lm=False, train_lm=False, ft_lr=3e-6, ft_epochs=3, ft_t
                lm_masked_out_mhsa_num_heads=8, lm_innner_input_nodes=512, lm_innner_output_nodes=512, lm_epochs=3,
                lm_max_len=20, just_nst=True)
 _BUILD = dict(compute_dtype="bf16", frontend_proj="utterance", pos_enc="none", use_group_norm=False,
-              specaug_ref_noop_masks=False, dp_world_size=1, layer_norm_eps=1e-5, bn_eps=1e-5, bn_momentum=0.1)
+              specaug_ref_noop_masks=False, dp_world_size=1, layer_norm_eps=1e-5, bn_eps=1e-5, bn_momentum=0.1, beam_size=0)
 
 
 class HParams:
@@ -107,6 +109,9 @@ class HParams:
 
     def set_blank_index(self, blank_idx):
         self.blank_idx = blank_idx
+
+    def set_beam_size(self, beam_size):
+        self.beam_size = int(beam_size)
 
     def set_ntokens(self, ntokens):
         self.ntokens = ntokens

@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from ... import specaugment as _sa
 from ...conformer import Conformer
-from ...ctc import greedy_decode as _greedy_decode
+from ...ctc import beam_search_decode as _beam_search_decode, greedy_decode as _greedy_decode
 from ...frontend import frame_frontend as _frame_frontend, linear as _linear, projection_block as _projection_block
 from ...lstm import LSTM
 from ..convsubsampling import ConvSubSampling
@@ -79,6 +79,17 @@ class ASRNN(nn.Module):
         (cfm_ctc_greedy_decode: first maximum wins, exactly torch.argmax's rule)."""
         ids, _, _ = _greedy_decode(x.float() if x.dtype != torch.float32 else x, compact=False)
         return ids
+
+    def predict_beam(self, x, lengths=None, beam_size=16, pad=None):
+        """Best CTC prefix-beam-search hypothesis per utterance (cfm_ctc_beam_decode) in place of the argmax:
+        (tokens (B, T) int32 padded with -1, n (B,)) with <pad>/<blank> never emitted -- the form
+        Vocab.decode(batch, lengths) takes.  lengths: the valid frames per utterance (None: all); pad: the <pad> id
+        (None: hp.pad_idx if set, else none)."""
+        if pad is None:
+            pad = int(getattr(self.hp, "pad_idx", -1))
+        toks, n, _ = _beam_search_decode(x.float() if x.dtype != torch.float32 else x, lengths, beam_size=beam_size,
+                                         blank=int(self.hp.blank_idx), pad=pad, nbest=1)
+        return toks[:, 0], n[:, 0]
 
     def conformer_blocks(self, x, lengths=None):
         """asrnn.py:60-71 (kept for API parity): x (B, T, d) through the Conformer layers in turn."""

@@ -12,6 +12,9 @@ Same constructor, methods and control flow as the reference; what runs underneat
                collapse, the reference's Vocab.decode rule) -> only surviving ids go to the host.
                Under torch.distributed (world > 1) the batches are sharded round-robin over the ranks
                and the label lists are all-gathered back into batch order.
+  beam         hp.beam_size > 0 (default 0: the paths above, unchanged): the metric and the pseudo-labels decode
+               with ctc.beam_search_decode (CTC prefix beam search on the device, best hypothesis, <pad> never
+               emitted, the model's output lengths) instead of the argmax.
   WER          myvocab.wer (jiwer's sentence-list WER; jiwer is not in this image)
 
 Dropped (outside the hot path): tqdm colours, Evals plots (losses / WER are kept on
@@ -28,7 +31,7 @@ from statistics import mean
 import torch
 import torch.nn as nn
 
-from ...ctc import CTCLoss, greedy_decode
+from ...ctc import CTCLoss, beam_search_decode, greedy_decode
 from ...optim import Adafactor
 from .myvocab import wer
 
@@ -85,7 +88,20 @@ class Runner:
         raise NotImplementedError("language-model fusion (runner.py:78-101) is outside the MI355X hot path")
 
     # ----------------------------------------------------------------------------- train / test
-    def _metric(self, dataset, logits, target):
+    def _beam_labels(self, voc, logits, lengths):
+        """hp.beam_size > 0: the best prefix-beam-search hypothesis per utterance as label strings (lengths: the
+        model's output lengths, padded / truncated to the batch; the kernel clamps them to [0, T])."""
+        if lengths is not None:
+            B = logits.shape[0]
+            lengths = nn.functional.pad(lengths[:B], (0, max(0, B - lengths.shape[0])))
+        toks, cnt, _ = beam_search_decode(logits.float() if logits.dtype != torch.float32 else logits, lengths,
+                                          beam_size=int(self.hp.beam_size), blank=voc.blank_idx, pad=voc.pad_idx)
+        return voc.decode(toks[:, 0], cnt[:, 0])
+
+    def _metric(self, dataset, logits, target, lengths=None):
+        if getattr(self.hp, "beam_size", 0) > 0:
+            tw, pw = _word_lists(dataset.vocab.decode(target), self._beam_labels(dataset.vocab, logits, lengths))
+            return wer(tw, pw) * 100 if tw else 0.0
         predicted = self.model.predict(logits)
         t_strs = dataset.vocab.decode(target)
         p_strs = dataset.vocab.decode(predicted)
@@ -115,7 +131,7 @@ class Runner:
                 self.optimizer.step()
                 eloss.append(cur)
                 if want_wer:
-                    emetric.append(self._metric(train_set, logits.detach(), target))
+                    emetric.append(self._metric(train_set, logits.detach(), target, output_lengths))
             self._check_device_errors()
             self.history["loss"].append(mean([100 if isnan(x) else x for x in eloss]))
             self.history["metric"].append(mean(emetric) if emetric else float("nan"))
@@ -142,7 +158,7 @@ class Runner:
                 output_lens = output_lens.clamp(max=logits.shape[1])
                 loss = self.loss(logits.transpose(0, 1), target, output_lens, target_lens)
                 eloss.append(loss.item())
-                emetric.append(self._metric(test_set, logits, target))
+                emetric.append(self._metric(test_set, logits, target, output_lens))
         self._check_device_errors()
         eloss = mean([100 if isnan(x) else x for x in eloss])
         return eloss, mean(emetric)
@@ -160,7 +176,10 @@ class Runner:
         with torch.no_grad():
             for i in range(rank, n, world):
                 batch = dataset.get_batch(i, "pretrain")["input"]
-                logits, _ = self.model(batch["mels"], batch["tau"])
+                logits, out_lens = self.model(batch["mels"], batch["tau"])
+                if getattr(self.hp, "beam_size", 0) > 0:
+                    mine[i] = self._beam_labels(voc, logits, out_lens)
+                    continue
                 # ASRNN.predict + Vocab.decode in one device pass: argmax, <pad>/<blank> removed, no collapse
                 _, toks, cnt = greedy_decode(logits, None, blank=voc.blank_idx, pad=voc.pad_idx, collapse=False)
                 mine[i] = voc.decode(toks, cnt)

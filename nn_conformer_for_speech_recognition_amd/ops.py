@@ -1069,3 +1069,20 @@ def ctc_greedy_decode(x, lengths_i32=None, blank=0, pad=-1, collapse=False, batc
     L.call("cfm_ctc_greedy_decode", L.ptr(x), sb, st, L.ptr(lengths_i32), B, T, x.shape[-1], int(blank), int(pad),
            int(bool(collapse)), L.ptr(ids), L.ptr(out), L.ptr(out_len), L.stream())
     return ids, out, out_len
+
+
+def ctc_beam_decode(x, lengths_i32=None, beam=16, blank=0, pad=-1, nbest=1, batch_first=True):
+    """CTC prefix beam search (cfm_ctc_beam_decode) -> tokens (B, nbest, T) int32 padded with -1, lengths (B, nbest)
+    int32, scores (B, nbest) fp32, and the back-pointer table bp_parent / bp_token (B, T, beam) int32."""
+    B, T, sb, st = _rows(x, batch_first)
+    dev = x.device
+    bp_parent = torch.empty(B, T, beam, device=dev, dtype=torch.int32)
+    bp_token = torch.empty(B, T, beam, device=dev, dtype=torch.int32)
+    tokens = torch.empty(B, nbest, T, device=dev, dtype=torch.int32)
+    out_len = torch.empty(B, nbest, device=dev, dtype=torch.int32)
+    score = torch.empty(B, nbest, device=dev, dtype=torch.float32)
+    ws = workspace(L.size_call("cfm_ctc_beam_ws_bytes", B, T, int(beam)), dev)
+    L.call("cfm_ctc_beam_decode", L.ptr(x), sb, st, L.ptr(lengths_i32), B, T, x.shape[-1], int(blank), int(pad),
+           int(beam), int(nbest), L.ptr(bp_parent), L.ptr(bp_token), L.ptr(tokens), L.ptr(out_len), L.ptr(score),
+           L.ptr(ws), L.stream())
+    return tokens, out_len, score, bp_parent, bp_token
