@@ -751,6 +751,41 @@ int cfm_ctc_beam_decode(const float* logits, long sb, long st, const int32_t* le
                         int blank, int pad, int beam, int nbest, int32_t* bp_parent, int32_t* bp_token,
                         int32_t* tokens, int32_t* out_len, float* score, void* ws, void* stream);
 
+/* The same search with a back-off n-gram language model (order <= 3) fused in at every extension: shallow fusion,
+ * for the argmax call sites runner.py:150,220,275.  The reference names LM fusion only (runner.py:78-101: a
+ * transformer LM whose weights are added under keys that match nothing, never realised); this is the n-gram form.
+ *   extend  p_nb'(l+c) (+)= r[c] + alpha * lm(c | h(l)) + beta + (c == last(l) ? p_b(l) : (p_b (+) p_nb)(l))
+ * with h(l) the last min(order - 1, |l| + 1) symbols of <s> + l (<s> = V, </s> = V + 1) and lm the natural-log
+ * back-off probability; stays are unchanged, blank and pad are never scored.  Every live entry is extended by the
+ * K = min(token_beam, #tokens) acoustically best tokens of the frame (raw fp32 logits, lower id first among equals),
+ * merges are taken over all tokens; beam + beam * K <= 1024 and K <= 768 (CFM_ERR_UNSUPPORTED otherwise).  The beam
+ * ranks on the fused score and `score` is the fused score; eos != 0 adds alpha * lm(</s> | h(l)) to the final scores
+ * and orders the hypotheses by them (bp_* slots stay in the last frame's order); lens[b] == 0: one empty hypothesis
+ * of score alpha * lm(</s> | <s>) (0 without eos).
+ * cfm_ngram_lm (device pointers; nn_conformer_for_speech_recognition_amd/lm.py packs it): unigrams (V + 2) x {float
+ * logp, float backoff}; table (mask + 1) x 16-byte slots {uint64 key, float logp, float backoff}, open-addressed,
+ * mask + 1 a power of two, every key within `probe` <= 4 slots of its home
+ *   z = (key ^ seed) * 0x9E3779B97F4A7C15; z = (z ^ z >> 32) * 0xBF58476D1CE4E5B9; home = (z ^ z >> 29) & mask;
+ * key = n << 45 | a << 30 | b << 15 | c for the n-gram (a, b, c) (a bigram: a = 0), empty slots all ones.  Every
+ * index the kernel forms from a hash, a table word or a token id is masked or clamped before use: a malformed table
+ * gives wrong scores, never an out-of-range access.  ws: cfm_ctc_beam_lm_ws_bytes(B, T, beam, K).  Three launches,
+ * no host synchronisation (graph-capturable), bit-identical from run to run; with alpha = beta = 0, no eos and
+ * token_beam = beam + 1 the results are cfm_ctc_beam_decode's. */
+typedef struct cfm_ngram_lm {
+  const void* unigrams;
+  const void* table;
+  uint64_t seed;
+  uint32_t mask;
+  int probe;
+  int order;
+  int V;
+} cfm_ngram_lm;
+size_t cfm_ctc_beam_lm_ws_bytes(int B, int T, int W, int K);
+int cfm_ctc_beam_decode_lm(const float* logits, long sb, long st, const int32_t* lens, int B, int T, int V,
+                           int blank, int pad, int beam, int nbest, int token_beam, float alpha, float beta, int eos,
+                           const cfm_ngram_lm* lm, int32_t* bp_parent, int32_t* bp_token, int32_t* tokens,
+                           int32_t* out_len, float* score, void* ws, void* stream);
+
 /* BiLSTM decoder recurrence: replaces the cuDNN/MIOpen recurrence of the
  * reference's nn.LSTM (asrnn.py:38 construct, :252 call on the 2-D encoder output = ONE unbatched
  * sequence of L = B*T_enc steps).  Gate order i, f, g, o (torch).  One cooperative launch per pass;

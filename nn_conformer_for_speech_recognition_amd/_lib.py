@@ -22,6 +22,12 @@ c_void_p, c_int, c_long, c_float, c_size_t = ctypes.c_void_p, ctypes.c_int, ctyp
 c_u64 = ctypes.c_uint64
 
 
+class NGramLMDesc(ctypes.Structure):
+    """cfm_ngram_lm (include/cfm.h)."""
+    _fields_ = [("unigrams", c_void_p), ("table", c_void_p), ("seed", c_u64), ("mask", ctypes.c_uint32),
+                ("probe", c_int), ("order", c_int), ("V", c_int)]
+
+
 class GemmDesc(ctypes.Structure):
     _fields_ = [
         ("M", c_int), ("N", c_int), ("K", c_int), ("batch", c_int),
@@ -260,6 +266,10 @@ _SIGS = {
     "cfm_ctc_beam_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "cfm_ctc_beam_decode": (c_int, [c_void_p, c_long, c_long, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cfm_ctc_beam_lm_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "cfm_ctc_beam_decode_lm": (c_int, [c_void_p, c_long, c_long, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                       c_int, c_int, c_float, c_float, c_int, ctypes.POINTER(NGramLMDesc), c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cfm_lstm_ws_bytes": (c_size_t, [c_int, c_int]),   # (H, ndir)
     "cfm_lstm_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                              c_void_p]),

@@ -1,4 +1,4 @@
-// ctc_beam.hip — CTC prefix beam search (no language model) on the device.
+// ctc_beam.hip — CTC prefix beam search on the device, without a language model or with a back-off n-gram fused in.
 //
 //   cfm_ctc_beam_decode is the alternative to the per-frame argmax of ASRNN.predict (asrnn.py:48-58) and of the
 //   Runner's metric / pseudo-label passes (runner.py:150,220,275): instead of following one alignment it sums the
@@ -25,6 +25,24 @@
 //                  entry, the offset accumulated in double.  Back-pointers go out with ordinary vector stores.
 //   beam_backtrace one wave per utterance: the back-pointer table staged through LDS in chunks of frames, one lane
 //                  per hypothesis walking it (once to count, once to write).
+//
+// cfm_ctc_beam_decode_lm fuses a back-off n-gram LM (order <= 3; lm.py packs it) into the search: shallow fusion, which
+// the reference only names (runner.py:78-101 adds a transformer LM's weights under keys that match nothing).  The
+// extension becomes r[c] + alpha * lm(c | h(l)) + beta + ..., h(l) the last min(N - 1, |l| + 1) symbols of <s> + l.
+// beam_search<true> differs from the kernel above in four places:
+//   candidates     an LM term breaks the base_a + r[c_b] ordering the pair rule rests on, so every entry is extended
+//                  by the K = token_beam acoustically best tokens: W + W K candidates (<= 1024), owner / start are a
+//                  division;
+//   LM term        alpha * lm + beta is a function of the prefix alone: it is kept with the entry (lt) so that an
+//                  extension merging into a live entry adds the same term; per candidate the probes (u, v, c),
+//                  (v, c) and uni[c] are independent loads issued together, each probe reading its 4 slots
+//                  unconditionally and selecting afterwards; the context back-offs bo(u, v), bo(v) belong to the
+//                  entry and are fetched where r[last] is gathered, into LDS;
+//   fault safety   every index formed from a hash, a table word or a token id is masked with the capacity mask or
+//                  clamped to [0, V + 1] before it addresses memory: a malformed table gives wrong scores, never an
+//                  out-of-range access;
+//   sentence end   the final scores add alpha * lm(</s> | h(l)) (eos) and a W-element rank count writes the slot
+//                  permutation beam_backtrace follows (null: identity, the no-LM order).
 #include "cfm_common.h"
 
 #include <math.h>
@@ -39,6 +57,60 @@ __device__ __forceinline__ float lse2(float a, float b) {
   const float m = fmaxf(a, b);
   if (m == NEG_INF) return NEG_INF;
   return m + logf(expf(a - m) + expf(b - m));
+}
+
+// ------------------------------------------------------------------------------------------ n-gram tables
+struct LmP {
+  const float2* uni;     // (V + 2) {logp, backoff}
+  const uint4* tab;      // (mask + 1) slots {key lo, key hi, logp, backoff}
+  uint64_t seed;
+  uint32_t mask;
+  int probe, order, V;
+  float alpha, beta;
+  int eos;               // add alpha * lm(</s> | h) to the final scores
+};
+
+__device__ __forceinline__ uint64_t lm_key2(int v, int c) { return (2ull << 45) | ((uint64_t)v << 15) | (uint64_t)c; }
+__device__ __forceinline__ uint64_t lm_key3(int u, int v, int c) {
+  return (3ull << 45) | ((uint64_t)u << 30) | ((uint64_t)v << 15) | (uint64_t)c;
+}
+__device__ __forceinline__ int lm_id(int c, int V) { return min(max(c, 0), V + 1); }
+
+struct LmHit { float lp, bo; bool hit; };
+// all four slots are loaded whatever they hold (a load that depends on the previous slot's key would serialise L2
+// round trips); the slot index is masked, so any table word is a safe address
+__device__ __forceinline__ LmHit lm_probe(const LmP& lm, uint64_t key) {
+  uint64_t z = (key ^ lm.seed) * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 32)) * 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 29;
+  const uint32_t h = (uint32_t)z & lm.mask;
+  uint4 s[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) s[j] = lm.tab[(h + (uint32_t)j) & lm.mask];
+  LmHit r{0.f, 0.f, false};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const uint64_t k = ((uint64_t)s[j].y << 32) | (uint64_t)s[j].x;
+    if (j < lm.probe && k == key) { r.lp = __uint_as_float(s[j].z); r.bo = __uint_as_float(s[j].w); r.hit = true; }
+  }
+  return r;
+}
+// lm(c | u, v): u < 0: the context is (v) alone; bo2 = bo(u, v), bo1 = bo(v) (0 where the order has no such context)
+__device__ __forceinline__ float lm_score(const LmP& lm, int u, int v, int c, float bo2, float bo1) {
+  const int cu = lm_id(u, lm.V), cv = lm_id(v, lm.V), cc = lm_id(c, lm.V);
+  const LmHit t = lm_probe(lm, lm_key3(cu, cv, cc));
+  const LmHit d = lm_probe(lm, lm_key2(cv, cc));
+  const float2 g = lm.uni[cc];
+  const float low = (lm.order >= 2 && d.hit) ? d.lp : bo1 + g.x;
+  return (lm.order >= 3 && u >= 0 && t.hit) ? t.lp : bo2 + low;
+}
+// the back-offs of an entry's context: u < 0: no second symbol
+__device__ __forceinline__ void lm_context(const LmP& lm, int u, int v, float& bo2, float& bo1) {
+  const int cu = lm_id(u, lm.V), cv = lm_id(v, lm.V);
+  const LmHit d = lm_probe(lm, lm_key2(cu, cv));
+  const float2 g = lm.uni[cv];
+  bo1 = lm.order >= 2 ? g.y : 0.f;
+  bo2 = (lm.order >= 3 && u >= 0 && d.hit) ? d.bo : 0.f;
 }
 
 __device__ __forceinline__ int clamp_len(const int32_t* lens, int b, int T) {
@@ -116,10 +188,12 @@ __global__ __launch_bounds__(256) void beam_topk(const float* __restrict__ x, lo
 struct BeamP {
   const float* x; long sb, st;
   const int32_t* lens;
-  int B, T, V, W, K, KP, NC, NP, NE;   // NC = W stays + NE extensions; NP = NC rounded up to a power of two >= 16
+  int B, T, V, W, K, KP, NC, NP, NE;   // NC = W stays + NE extensions; NP = NC rounded up to a power of two >= 16 (LM: to a multiple of 16)
   const float* row_lse; const float* row_rb; const int32_t* tk; const float* tlp;
   int32_t* bp_parent; int32_t* bp_token;
   float* fin;                          // (B, W) final scores
+  int32_t* perm;                       // LM: (B, W) slots in descending final score
+  LmP lm;
 };
 
 __device__ __forceinline__ uint64_t prefix_mix(uint64_t h, int c) {
@@ -139,6 +213,7 @@ __host__ __device__ __forceinline__ int ext_count(int i, int W, int K) {
   return n < K ? n : K;
 }
 
+template <bool LM>
 __global__ __launch_bounds__(256) void beam_search(const BeamP p) {
   extern __shared__ __align__(16) unsigned char beam_sm[];
   const int W = p.W, K = p.K, KP = p.KP, NP = p.NP, NC = p.NC;
@@ -160,18 +235,35 @@ __global__ __launch_bounds__(256) void beam_search(const BeamP p) {
   int* start = last + 2 * W;                                     // [W]  first extension candidate of beam rank i
   int* sel = start + W;                                          // [W]  candidate index of the new slot s
   int* parent_of = sel + W;                                      // [W]  slot of entry k's prefix less its last label
-  int* owner = parent_of + W;                                    // [NE] beam rank of extension candidate e
+  int* owner = parent_of + W;                                    // [NE] beam rank of extension candidate e (no LM)
+  // LM: per entry the second-to-last symbol (<s> = V for a one-token prefix, -1 for the empty one), the stored LM
+  // term and the two context back-offs; per extension candidate its LM term
+  int* prev = owner + (LM ? 0 : p.NE);                           // [2][W]
+  float* lt = reinterpret_cast<float*>(prev + 2 * W);            // [2][W]
+  float* bo2 = lt + 2 * W;                                       // [W]
+  float* bo1 = bo2 + W;                                          // [W]
+  float* clt = bo1 + W;                                          // [NE]
 
   const int Tb = clamp_len(p.lens, b, p.T);
-  if (tid == 0) {
-    int acc = 0;
-    for (int i = 0; i < W; ++i) { start[i] = acc; acc += ext_count(i, W, K); }
+  if constexpr (!LM) {
+    if (tid == 0) {
+      int acc = 0;
+      for (int i = 0; i < W; ++i) { start[i] = acc; acc += ext_count(i, W, K); }
+    }
   }
   for (int i = tid; i < 2 * W; i += NT) {
     const bool root = i == 0;
     pb[i] = root ? 0.f : NEG_INF; pnb[i] = NEG_INF; tot[i] = root ? 0.f : NEG_INF;
     hash[i] = 0; phash[i] = 0; len[i] = 0; last[i] = -1;
     if (i < W) { rl[i] = NEG_INF; parent_of[i] = -1; }
+    if constexpr (LM) {
+      prev[i] = -1; lt[i] = 0.f;
+      if (i < W) {
+        float b2 = 0.f, b1 = 0.f;
+        if (root) lm_context(p.lm, -1, p.lm.V, b2, b1);
+        bo2[i] = b2; bo1[i] = b1;
+      }
+    }
   }
   if (Tb > 0)
     for (int j = tid; j < K; j += NT) {
@@ -179,9 +271,11 @@ __global__ __launch_bounds__(256) void beam_search(const BeamP p) {
       tlp[j] = p.tlp[(long)b * p.T * KP + j];
     }
   __syncthreads();
-  for (int i = tid; i < W; i += NT) {
-    const int n = ext_count(i, W, K);
-    for (int j = 0; j < n; ++j) owner[start[i] + j] = i;
+  if constexpr (!LM) {
+    for (int i = tid; i < W; i += NT) {
+      const int n = ext_count(i, W, K);
+      for (int j = 0; j < n; ++j) owner[start[i] + j] = i;
+    }
   }
   double off = 0.0;
   float rb_n = Tb > 0 ? p.row_rb[(long)b * p.T] : 0.f, lse_n = Tb > 0 ? p.row_lse[(long)b * p.T] : 0.f;
@@ -217,9 +311,19 @@ __global__ __launch_bounds__(256) void beam_search(const BeamP p) {
           if (lastc[idx] >= 0) c = pnbc[idx] + rl[idx];
         }
       } else if (idx < NC) {
-        const int e = idx - W, i = owner[e], j = e - start[i];
-        const int tokn = tkc[j];
-        if (totc[i] > NEG_INF && tokn >= 0) c = tlpc[j] + (tokn == lastc[i] ? pbc[i] : totc[i]);
+        if constexpr (LM) {
+          const int e = idx - W, i = e / K, j = e - i * K;
+          const int tokn = tkc[j];
+          const int li = lastc[i];
+          const float term = fmaf(p.lm.alpha, lm_score(p.lm, prev[cur * W + i], li >= 0 ? li : p.lm.V, tokn, bo2[i], bo1[i]),
+                                  p.lm.beta);
+          clt[e] = term;
+          if (totc[i] > NEG_INF && tokn >= 0) c = (tlpc[j] + term) + (tokn == li ? pbc[i] : totc[i]);
+        } else {
+          const int e = idx - W, i = owner[e], j = e - start[i];
+          const int tokn = tkc[j];
+          if (totc[i] > NEG_INF && tokn >= 0) c = tlpc[j] + (tokn == lastc[i] ? pbc[i] : totc[i]);
+        }
       }
       cpb[idx] = a;
       cpnb[idx] = c;
@@ -252,13 +356,16 @@ __global__ __launch_bounds__(256) void beam_search(const BeamP p) {
       const int par = parent_of[k];
       if (par < 0) continue;
       const int e = lastc[k];
-      cpnb[k] = lse2(cpnb[k], rl[k] + (lastc[par] == e ? pbc[par] : totc[par]));
-      const int n = ext_count(par, W, K);
+      if constexpr (LM)   // the entry's own LM term: the same sum as the candidate's, in the same order
+        cpnb[k] = lse2(cpnb[k], (rl[k] + lt[cur * W + k]) + (lastc[par] == e ? pbc[par] : totc[par]));
+      else
+        cpnb[k] = lse2(cpnb[k], rl[k] + (lastc[par] == e ? pbc[par] : totc[par]));
+      const int n = LM ? K : ext_count(par, W, K);
       int hit = -1;
 #pragma unroll 4
       for (int j = 0; j < n; ++j)
         if (tkc[j] == e) hit = j;
-      if (hit >= 0) cpnb[W + start[par] + hit] = NEG_INF;
+      if (hit >= 0) cpnb[W + (LM ? par * K : start[par]) + hit] = NEG_INF;
     }
     lds_barrier();
     for (int idx = tid; idx < NP; idx += NT) {
@@ -305,20 +412,34 @@ __global__ __launch_bounds__(256) void beam_search(const BeamP p) {
       if (!(sc > NEG_INF)) {
         pb[o] = NEG_INF; pnb[o] = NEG_INF; tot[o] = NEG_INF; hash[o] = 0; phash[o] = 0; len[o] = 0; last[o] = -1;
         rl[s] = NEG_INF;
+        if constexpr (LM) { prev[o] = -1; lt[o] = 0.f; bo2[s] = 0.f; bo1[s] = 0.f; }
       } else {
         int nl;
         if (idx < W) {
           par = idx;
           hash[o] = hc[par]; phash[o] = phc[par]; len[o] = lenc[par]; nl = lastc[par];
+          if constexpr (LM) { prev[o] = prev[cur * W + par]; lt[o] = lt[cur * W + par]; }
         } else {
           const int e = idx - W;
-          par = owner[e];
-          tokn = tkc[e - start[par]];
+          if constexpr (LM) {
+            par = e / K;
+            tokn = tkc[e - par * K];
+            prev[o] = lenc[par] > 0 ? lastc[par] : p.lm.V;
+            lt[o] = clt[e];
+          } else {
+            par = owner[e];
+            tokn = tkc[e - start[par]];
+          }
           hash[o] = prefix_mix(hc[par], tokn); phash[o] = hc[par]; len[o] = lenc[par] + 1; nl = tokn;
         }
         last[o] = nl;
         pb[o] = cpb[idx] - m; pnb[o] = cpnb[idx] - m; tot[o] = sc - m;
         rl[s] = (more && nl >= 0) ? xn[nl] - lse_n : NEG_INF;
+        if constexpr (LM) {
+          float b2, b1;
+          lm_context(p.lm, prev[o], nl >= 0 ? nl : p.lm.V, b2, b1);
+          bo2[s] = b2; bo1[s] = b1;
+        }
       }
       parent_of[s] = -1;
       p.bp_parent[row * W + s] = par;
@@ -332,14 +453,34 @@ __global__ __launch_bounds__(256) void beam_search(const BeamP p) {
     lds_barrier();
   }
   const float* totf = tot + (Tb & 1) * W;
-  for (int s = tid; s < W; s += NT)
-    p.fin[(long)b * W + s] = totf[s] > NEG_INF ? (float)(off + (double)totf[s]) : NEG_INF;
+  if constexpr (LM) {
+    // the </s> term, then the slots in descending final score (equal scores: lower slot first)
+    for (int s = tid; s < W; s += NT) {
+      const int o = (Tb & 1) * W + s;
+      const int nl = last[o];
+      const float e = p.lm.eos ? lm_score(p.lm, prev[o], nl >= 0 ? nl : p.lm.V, p.lm.V + 1, bo2[s], bo1[s]) : 0.f;
+      const float f = totf[s] > NEG_INF ? (float)(off + (double)totf[s] + (double)(p.lm.alpha * e)) : NEG_INF;
+      p.fin[(long)b * W + s] = f;
+      key[s] = ((uint64_t)f_order(f) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)s);
+    }
+    lds_barrier();
+    for (int s = tid; s < W; s += NT) {
+      const uint64_t mine = key[s];
+      int r = 0;
+      for (int k = 0; k < W; ++k) r += (int)(key[k] > mine);
+      p.perm[(long)b * W + r] = s;
+    }
+  } else {
+    for (int s = tid; s < W; s += NT)
+      p.fin[(long)b * W + s] = totf[s] > NEG_INF ? (float)(off + (double)totf[s]) : NEG_INF;
+  }
 }
 
 // ------------------------------------------------------------------------------------------ backtrace
 __global__ __launch_bounds__(64) void beam_backtrace(const int32_t* __restrict__ bp_parent,
                                                      const int32_t* __restrict__ bp_token,
                                                      const int32_t* __restrict__ lens, const float* __restrict__ fin,
+                                                     const int32_t* __restrict__ perm,   // null: hypothesis h is slot h
                                                      int B, int T, int W, int nbest, int32_t* __restrict__ tokens,
                                                      int32_t* __restrict__ out_len, float* __restrict__ score) {
   __shared__ int32_t sp[BT_LDS], stok[BT_LDS];
@@ -349,13 +490,15 @@ __global__ __launch_bounds__(64) void beam_backtrace(const int32_t* __restrict__
   const long base = (long)b * T * W;
   bool valid[2];
   int L[2] = {0, 0};
+  int slot[2];
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     const int h = lane + 64 * q;
-    valid[q] = h < nbest && h < W && Tb > 0 && bp_parent[base + (long)(Tb - 1) * W + h] >= 0;
+    slot[q] = (perm && h < W) ? min(max(perm[(long)b * W + h], 0), W - 1) : h;
+    valid[q] = h < nbest && h < W && Tb > 0 && bp_parent[base + (long)(Tb - 1) * W + slot[q]] >= 0;
   }
   for (int pass = 0; pass < 2; ++pass) {
-    int s[2] = {lane, lane + 64};
+    int s[2] = {slot[0], slot[1]};
     int pos[2] = {L[0], L[1]};
     for (int t1 = Tb; t1 > 0; t1 -= CH) {
       const int t0 = max(0, t1 - CH), n = (t1 - t0) * W;
@@ -388,7 +531,8 @@ __global__ __launch_bounds__(64) void beam_backtrace(const int32_t* __restrict__
     if (h >= nbest) continue;
     const bool first_empty = Tb == 0 && h == 0;
     out_len[(long)b * nbest + h] = valid[q] ? L[q] : 0;
-    score[(long)b * nbest + h] = valid[q] ? fin[(long)b * W + h] : (first_empty ? 0.f : NEG_INF);
+    score[(long)b * nbest + h] =
+        valid[q] ? fin[(long)b * W + slot[q]] : (first_empty ? (perm ? fin[(long)b * W + slot[q]] : 0.f) : NEG_INF);
   }
   for (int h = 0; h < nbest; ++h) {
     const int q = h >> 6;
@@ -448,12 +592,81 @@ CFM_EXPORT int cfm_ctc_beam_decode(const float* logits, long sb, long st, const 
   p.NP = np;
   p.row_lse = row_lse; p.row_rb = row_rb; p.tk = tk; p.tlp = tlp;
   p.bp_parent = bp_parent; p.bp_token = bp_token; p.fin = fin;
+  p.perm = nullptr; p.lm = LmP{};
   const size_t sh = sizeof(uint64_t) * ((size_t)np + 4 * W) +
                     sizeof(float) * (3 * (size_t)np + 7 * W + 2 * KP) +
                     sizeof(int) * (2 * (size_t)KP + 7 * W + (ne > 0 ? ne : 1));
   CFM_REQUIRE(sh <= 64 * 1024, CFM_ERR_UNSUPPORTED, "beam state exceeds the LDS budget");
-  hipLaunchKernelGGL(beam_search, dim3(B), dim3(np <= 128 ? 64 : 256), sh, s, p);
-  hipLaunchKernelGGL(beam_backtrace, dim3(B), dim3(64), 0, s, bp_parent, bp_token, lens, fin, B, T, W, nbest, tokens,
-                     out_len, score);
+  hipLaunchKernelGGL(beam_search<false>, dim3(B), dim3(np <= 128 ? 64 : 256), sh, s, p);
+  hipLaunchKernelGGL(beam_backtrace, dim3(B), dim3(64), 0, s, bp_parent, bp_token, lens, fin,
+                     static_cast<const int32_t*>(nullptr), B, T, W, nbest, tokens, out_len, score);
   return cfm::check_launch("cfm_ctc_beam_decode");
+}
+
+CFM_EXPORT size_t cfm_ctc_beam_lm_ws_bytes(int B, int T, int W, int K) {
+  if (B <= 0 || T <= 0 || W <= 0 || K <= 0) return 0;
+  const size_t bt = (size_t)B * T;
+  return sizeof(float) * (bt * (2 + 2 * (size_t)K) + 2 * (size_t)B * W);
+}
+
+CFM_EXPORT int cfm_ctc_beam_decode_lm(const float* logits, long sb, long st, const int32_t* lens, int B, int T, int V,
+                                      int blank, int pad, int beam, int nbest, int token_beam, float alpha, float beta,
+                                      int eos, const cfm_ngram_lm* lm, int32_t* bp_parent, int32_t* bp_token,
+                                      int32_t* tokens, int32_t* out_len, float* score, void* ws, void* stream) {
+  CFM_REQUIRE(logits && bp_parent && bp_token && tokens && out_len && score && ws, CFM_ERR_ARG, "null pointer");
+  CFM_REQUIRE(lm && lm->unigrams && lm->table, CFM_ERR_ARG, "null language-model table");
+  CFM_REQUIRE(B > 0 && T > 0, CFM_ERR_SHAPE, "bad shape");
+  CFM_REQUIRE(V >= 2 && V <= 16384, CFM_ERR_UNSUPPORTED, "2 <= V <= 16384");
+  CFM_REQUIRE(beam >= 1 && nbest >= 1 && nbest <= beam, CFM_ERR_ARG, "1 <= nbest <= beam");
+  CFM_REQUIRE(beam <= BEAM_MAX, CFM_ERR_UNSUPPORTED, "beam width must be <= 128");
+  CFM_REQUIRE(blank >= 0 && blank < V, CFM_ERR_ARG, "blank out of range");
+  CFM_REQUIRE(pad < V, CFM_ERR_ARG, "pad out of range");
+  CFM_REQUIRE(token_beam >= 1, CFM_ERR_ARG, "token_beam must be >= 1");
+  CFM_REQUIRE(lm->V == V, CFM_ERR_ARG, "the language model's V differs from the logits'");
+  CFM_REQUIRE(lm->order >= 1 && lm->order <= 3, CFM_ERR_UNSUPPORTED, "n-gram order must be 1..3");
+  CFM_REQUIRE(lm->probe >= 1 && lm->probe <= 4, CFM_ERR_UNSUPPORTED, "probe length must be 1..4");
+  CFM_REQUIRE((lm->mask & (lm->mask + 1u)) == 0u, CFM_ERR_ARG, "table capacity must be a power of two");
+  hipStream_t s = cfm::as_stream(stream);
+  const int W = beam;
+  const int ntok = V - 1 - ((pad >= 0 && pad != blank) ? 1 : 0);
+  const int K = ntok < token_beam ? ntok : token_beam;
+  CFM_REQUIRE(K >= 1, CFM_ERR_UNSUPPORTED, "no token left to emit");
+  CFM_REQUIRE(W + W * K <= 1024, CFM_ERR_UNSUPPORTED, "beam + beam * token_beam must be <= 1024");
+  CFM_REQUIRE(K <= 768, CFM_ERR_UNSUPPORTED, "token_beam must be <= 768");
+  const size_t bt = (size_t)B * T;
+  float* row_lse = static_cast<float*>(ws);
+  float* row_rb = row_lse + bt;
+  float* tlp = row_rb + bt;
+  int32_t* tk = reinterpret_cast<int32_t*>(tlp + bt * K);
+  float* fin = reinterpret_cast<float*>(tk + bt * K);
+  int32_t* perm = reinterpret_cast<int32_t*>(fin + (size_t)B * W);
+
+  const int wpb = V <= 4096 ? 4 : 1;
+  hipLaunchKernelGGL(beam_topk, dim3((unsigned)((bt + wpb - 1) / wpb)), dim3(64 * wpb),
+                     (size_t)wpb * V * sizeof(float), s, logits, sb, st, lens, B, T, V, blank, pad < 0 ? -1 : pad, K, K, row_lse, row_rb, tk, tlp);
+
+  BeamP p;
+  p.x = logits; p.sb = sb; p.st = st; p.lens = lens;
+  p.B = B; p.T = T; p.V = V; p.W = W; p.K = K; p.KP = K;
+  p.NE = W * K;
+  p.NC = W + p.NE;
+  const int np = (p.NC + 15) & ~15;   // the rank counting reads 16 keys per trip; padding costs candidates^2 work
+  p.NP = np;
+  p.row_lse = row_lse; p.row_rb = row_rb; p.tk = tk; p.tlp = tlp;
+  p.bp_parent = bp_parent; p.bp_token = bp_token; p.fin = fin; p.perm = perm;
+  p.lm.uni = static_cast<const float2*>(lm->unigrams);
+  p.lm.tab = static_cast<const uint4*>(lm->table);
+  p.lm.seed = lm->seed; p.lm.mask = lm->mask; p.lm.probe = lm->probe; p.lm.order = lm->order; p.lm.V = V;
+  p.lm.alpha = alpha; p.lm.beta = beta; p.lm.eos = eos ? 1 : 0;
+  // the layout of beam_search: the no-LM arrays with owner left out, then prev, lt, bo2, bo1, clt
+  const size_t sh = sizeof(uint64_t) * ((size_t)np + 4 * W) +
+                    sizeof(float) * (3 * (size_t)np + 7 * W + 2 * K) +
+                    sizeof(int) * (2 * (size_t)K + 7 * W) +
+                    sizeof(int) * (2 * (size_t)W) + sizeof(float) * (4 * (size_t)W + p.NE);
+  CFM_REQUIRE(sh <= 64 * 1024, CFM_ERR_UNSUPPORTED, "beam state exceeds the LDS budget");
+  // the next frame's token list is prefetched three per thread
+  hipLaunchKernelGGL(beam_search<true>, dim3(B), dim3((np <= 128 && K <= 192) ? 64 : 256), sh, s, p);
+  hipLaunchKernelGGL(beam_backtrace, dim3(B), dim3(64), 0, s, bp_parent, bp_token, lens, fin,
+                     static_cast<const int32_t*>(perm), B, T, W, nbest, tokens, out_len, score);
+  return cfm::check_launch("cfm_ctc_beam_decode_lm");
 }

@@ -10,8 +10,8 @@
                        logits gradient in the compute dtype straight into the head's two GEMMs).
   greedy_decode        ASRNN.predict (asrnn.py:48-58, argmax) + the id filter of Vocab.decode
                        (myvocab.py:211-231: <pad>/<blank> dropped, no repeat collapse by default).
-  beam_search_decode   CTC prefix beam search without a language model: the alternative to that argmax
-                       (modelled on torchaudio's CUDA CTC decoder).
+  beam_search_decode   CTC prefix beam search: the alternative to that argmax (modelled on torchaudio's CUDA
+                       CTC decoder), alone or with a back-off n-gram language model (lm.NGramLM) fused in.
 
 Everything is stream-ordered with no host synchronisation when targets are padded (B, S) and the
 lengths are device tensors, so a whole training step can be captured into one HIP graph.
@@ -188,14 +188,27 @@ def greedy_decode(logits, lengths=None, blank=0, pad=-1, collapse=False, batch_f
 
 
 BEAM_MAX = 128
+LM_CANDIDATES = 1024      # stays + extensions per frame of the LM search
+
+
+def default_token_beam(beam_size, n_tokens):
+    """min(W + 1, #tokens, 1024 // W - 1): the tokens each live entry is extended by when an LM is fused."""
+    return max(1, min(beam_size + 1, n_tokens, LM_CANDIDATES // beam_size - 1))
 
 
 def beam_search_decode(logits, lengths=None, beam_size=16, blank=0, pad=-1, nbest=1, batch_first=True,
-                       return_trace=False):
-    """CTC prefix beam search on the device (cfm_ctc_beam_decode; no language model).
+                       return_trace=False, lm=None, lm_weight=0.0, word_bonus=0.0, token_beam=None, lm_eos=True):
+    """CTC prefix beam search on the device (cfm_ctc_beam_decode; with `lm` cfm_ctc_beam_decode_lm).
     Returns (tokens (B, nbest, T) int32 padded with -1, lens (B, nbest) int32, scores (B, nbest) fp32 = log of
     the summed alignment probability the beam kept for each hypothesis), best first; with return_trace also
-    (bp_parent, bp_token) (B, T, beam_size) int32, the back-pointer table.  `pad` (< 0: none) is never emitted."""
+    (bp_parent, bp_token) (B, T, beam_size) int32, the back-pointer table.  `pad` (< 0: none) is never emitted.
+
+    lm: an lm.NGramLM over the same ids (lm.V == V, the same blank and pad), fused at every extension:
+    score(l + c) gains lm_weight * lm(c | context) + word_bonus; each live entry is extended by the `token_beam`
+    acoustically best tokens of the frame (None: default_token_beam; beam_size * (1 + token_beam) <= 1024); the
+    beam ranks on, and `scores` are, the fused scores.  lm_eos (only where the LM has </s>): the final scores add
+    lm_weight * lm(</s> | context) and order the hypotheses; the back-pointer slots keep the last frame's order.
+    With lm=None the other LM arguments must be at their defaults and the call is the plain search."""
     if not isinstance(beam_size, int) or isinstance(beam_size, bool) or not 1 <= beam_size <= BEAM_MAX:
         raise ValueError(f"beam_size must be an integer in [1, {BEAM_MAX}], got {beam_size!r}")
     if not isinstance(nbest, int) or isinstance(nbest, bool) or not 1 <= nbest <= beam_size:
@@ -211,7 +224,29 @@ def beam_search_decode(logits, lengths=None, beam_size=16, blank=0, pad=-1, nbes
     x = logits if logits.stride(-1) == 1 else logits.contiguous()
     B = x.shape[0] if batch_first else x.shape[1]
     ln = None if lengths is None else _lengths(lengths, B, x.device)
-    tokens, lens, scores, bp_parent, bp_token = ops.ctc_beam_decode(x, ln, beam_size, blank, pad, nbest, batch_first)
+    if lm is None:
+        if lm_weight != 0.0 or word_bonus != 0.0 or token_beam is not None or lm_eos is not True:
+            raise ValueError("lm_weight, word_bonus, token_beam and lm_eos need an lm")
+        tokens, lens, scores, bp_parent, bp_token = ops.ctc_beam_decode(x, ln, beam_size, blank, pad, nbest,
+                                                                        batch_first)
+    else:
+        if lm.V != V:
+            raise ValueError(f"the language model is over {lm.V} ids, the logits over {V}")
+        if lm.blank != blank or max(lm.pad, -1) != max(pad, -1):
+            raise ValueError(f"the language model's blank / pad ({lm.blank}, {lm.pad}) differ from the call's "
+                             f"({blank}, {pad})")
+        n_tokens = V - 1 - (1 if 0 <= pad != blank else 0)
+        if token_beam is None:
+            token_beam = default_token_beam(beam_size, n_tokens)
+        if not isinstance(token_beam, int) or isinstance(token_beam, bool) or token_beam < 1:
+            raise ValueError(f"token_beam must be a positive integer, got {token_beam!r}")
+        K = min(token_beam, n_tokens)
+        if K < 1 or beam_size * (1 + K) > LM_CANDIDATES or K > 768:
+            raise ValueError(f"beam_size * (1 + token_beam) must be <= {LM_CANDIDATES} and token_beam <= 768, got "
+                             f"beam_size {beam_size}, token_beam {K}")
+        tokens, lens, scores, bp_parent, bp_token = ops.ctc_beam_decode_lm(
+            x, lm.device_tables(x.device), ln, beam_size, K, lm_weight, word_bonus, bool(lm_eos) and lm.has_eos,
+            blank, pad, nbest, batch_first)
     if return_trace:
         return tokens, lens, scores, (bp_parent, bp_token)
     return tokens, lens, scores

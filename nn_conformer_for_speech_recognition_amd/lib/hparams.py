@@ -15,6 +15,10 @@ MI355X build (documented in DESIGN.md):
   dp_world_size          int               set by the data-parallel launcher
   beam_size              int               0: the reference's argmax decode; > 0: the Runner's metric and pseudo-label
                                            passes decode with a CTC prefix beam search of that width (set_beam_size)
+  decoder_lm             lm.NGramLM | None an n-gram LM fused into that beam search (set_decoder_lm), weighted by
+  lm_weight, word_bonus  float             lm_weight, plus word_bonus per emitted token; token_beam: the tokens each
+  token_beam             int               entry is extended by (0: the default rule).  Not the reference's hp.lm
+                                           flag, which means "train the transformer LM"
 """
 from __future__ import annotations
 
@@ -59,7 +63,8 @@ _NST_LM = dict(nst=True, lm=False, train_lm=False, ft_lr=3e-6, ft_epochs=3, ft_t
                lm_masked_out_mhsa_num_heads=8, lm_innner_input_nodes=512, lm_innner_output_nodes=512, lm_epochs=3,
                lm_max_len=20, just_nst=True)
 _BUILD = dict(compute_dtype="bf16", frontend_proj="utterance", pos_enc="none", use_group_norm=False,
-              specaug_ref_noop_masks=False, dp_world_size=1, layer_norm_eps=1e-5, bn_eps=1e-5, bn_momentum=0.1, beam_size=0)
+              specaug_ref_noop_masks=False, dp_world_size=1, layer_norm_eps=1e-5, bn_eps=1e-5, bn_momentum=0.1, beam_size=0,
+              decoder_lm=None, lm_weight=0.0, word_bonus=0.0, token_beam=0)
 
 
 class HParams:
@@ -112,6 +117,12 @@ class HParams:
 
     def set_beam_size(self, beam_size):
         self.beam_size = int(beam_size)
+
+    def set_decoder_lm(self, lm, lm_weight=0.0, word_bonus=0.0, token_beam=0):
+        """Fuse an lm.NGramLM into the beam search of the metric and pseudo-label passes (needs beam_size > 0);
+        lm=None clears it."""
+        self.decoder_lm = lm
+        self.lm_weight, self.word_bonus, self.token_beam = float(lm_weight), float(word_bonus), int(token_beam)
 
     def set_ntokens(self, ntokens):
         self.ntokens = ntokens

@@ -80,15 +80,18 @@ class ASRNN(nn.Module):
         ids, _, _ = _greedy_decode(x.float() if x.dtype != torch.float32 else x, compact=False)
         return ids
 
-    def predict_beam(self, x, lengths=None, beam_size=16, pad=None):
+    def predict_beam(self, x, lengths=None, beam_size=16, pad=None, lm=None, lm_weight=0.0, word_bonus=0.0,
+                     token_beam=None):
         """Best CTC prefix-beam-search hypothesis per utterance (cfm_ctc_beam_decode) in place of the argmax:
         (tokens (B, T) int32 padded with -1, n (B,)) with <pad>/<blank> never emitted -- the form
         Vocab.decode(batch, lengths) takes.  lengths: the valid frames per utterance (None: all); pad: the <pad> id
-        (None: hp.pad_idx if set, else none)."""
+        (None: hp.pad_idx if set, else none).  lm: an lm.NGramLM fused into the search (cfm_ctc_beam_decode_lm) with
+        lm_weight, word_bonus and token_beam as in ctc.beam_search_decode."""
         if pad is None:
             pad = int(getattr(self.hp, "pad_idx", -1))
         toks, n, _ = _beam_search_decode(x.float() if x.dtype != torch.float32 else x, lengths, beam_size=beam_size,
-                                         blank=int(self.hp.blank_idx), pad=pad, nbest=1)
+                                         blank=int(self.hp.blank_idx), pad=pad, nbest=1, lm=lm, lm_weight=lm_weight,
+                                         word_bonus=word_bonus, token_beam=token_beam)
         return toks[:, 0], n[:, 0]
 
     def conformer_blocks(self, x, lengths=None):

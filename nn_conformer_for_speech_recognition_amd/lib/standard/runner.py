@@ -14,11 +14,12 @@ Same constructor, methods and control flow as the reference; what runs underneat
                and the label lists are all-gathered back into batch order.
   beam         hp.beam_size > 0 (default 0: the paths above, unchanged): the metric and the pseudo-labels decode
                with ctc.beam_search_decode (CTC prefix beam search on the device, best hypothesis, <pad> never
-               emitted, the model's output lengths) instead of the argmax.
+               emitted, the model's output lengths) instead of the argmax; with hp.decoder_lm (set_decoder_lm)
+               an n-gram LM is fused into that search (hp.lm_weight, hp.word_bonus, hp.token_beam).
   WER          myvocab.wer (jiwer's sentence-list WER; jiwer is not in this image)
 
 Dropped (outside the hot path): tqdm colours, Evals plots (losses / WER are kept on
-the Runner as .history and written to hp.plots_dir/history.json), the language-model fusion.
+the Runner as .history and written to hp.plots_dir/history.json), the transformer-LM weight fusion (fuse_models).
 """
 from __future__ import annotations
 
@@ -85,7 +86,8 @@ class Runner:
         self.model.to(self.hp.device)
 
     def fuse_models(self, lm_path):
-        raise NotImplementedError("language-model fusion (runner.py:78-101) is outside the MI355X hot path")
+        raise NotImplementedError("the transformer-LM weight fusion (runner.py:78-101) is outside the MI355X hot "
+                                  "path; for n-gram shallow fusion in the decoder see HParams.set_decoder_lm")
 
     # ----------------------------------------------------------------------------- train / test
     def _beam_labels(self, voc, logits, lengths):
@@ -94,8 +96,13 @@ class Runner:
         if lengths is not None:
             B = logits.shape[0]
             lengths = nn.functional.pad(lengths[:B], (0, max(0, B - lengths.shape[0])))
+        kw = {}
+        lm = getattr(self.hp, "decoder_lm", None)
+        if lm is not None:
+            kw = dict(lm=lm, lm_weight=float(self.hp.lm_weight), word_bonus=float(self.hp.word_bonus),
+                      token_beam=int(self.hp.token_beam) or None)
         toks, cnt, _ = beam_search_decode(logits.float() if logits.dtype != torch.float32 else logits, lengths,
-                                          beam_size=int(self.hp.beam_size), blank=voc.blank_idx, pad=voc.pad_idx)
+                                          beam_size=int(self.hp.beam_size), blank=voc.blank_idx, pad=voc.pad_idx, **kw)
         return voc.decode(toks[:, 0], cnt[:, 0])
 
     def _metric(self, dataset, logits, target, lengths=None):
