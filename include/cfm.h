@@ -509,6 +509,43 @@ int cfm_gn_silu_bwd(const void* dz, int dtype_dz, const float* y, const float* g
                     const float* mean, const float* rstd, float* dy, float* dgamma, float* dbeta, float* coef,
                     int B, int T, int C, float* ws, void* stream);
 
+/* Which kernels the conv-module entry points above launch (csrc/convmod.hip), as a pure host function. */
+enum cfm_convmod_op {
+  CFM_CONVMOD_OP_FWD = 0,                 /* cfm_glu_dwconv_fwd */
+  CFM_CONVMOD_OP_BWD = 1,                 /* cfm_glu_dwconv_bwd */
+  CFM_CONVMOD_OP_BWD_BN = 2,              /* cfm_glu_dwconv_bwd_bn */
+  CFM_CONVMOD_OP_BWD_GN = 3               /* cfm_glu_dwconv_bwd_gn */
+};
+enum cfm_convmod_family {
+  CFM_CONVMOD_FAM_UNSUPPORTED = 0,        /* the entry point returns CFM_ERR_UNSUPPORTED */
+  CFM_CONVMOD_FAM_VEC = 1,                /* 4 channels per lane through LDS: bf16 a (and da), C % 4 == 0, compiled K */
+  CFM_CONVMOD_FAM_SCALAR_KT = 2,          /* one channel per lane, K a template parameter (3, 5, 7, 15, 31, 33) */
+  CFM_CONVMOD_FAM_SCALAR_KRT = 3          /* one channel per lane, K at run time (any odd K <= 63; no folded backward) */
+};
+enum cfm_convmod_apply {
+  CFM_CONVMOD_APPLY_NONE = 0,             /* no z pointer in the query */
+  CFM_CONVMOD_APPLY_SCALAR = 1,           /* grid-stride, one element per thread per iteration: any C, any alignment */
+  CFM_CONVMOD_APPLY_VEC8 = 2              /* 8 elements per thread: C % 8 == 0, y and z 16-byte aligned */
+};
+typedef struct {
+  int op;                                 /* cfm_convmod_op */
+  int norm;                               /* the apply kernel's norm: 0 BatchNorm (cfm_bn_silu_fwd, cfm_bn_fwd), 1 GroupNorm */
+  int dtype_a, dtype_da, dtype_dz, dtype_z;
+  long M;                                 /* rows of y / z (B*T) */
+  int C, K;
+  const void* y;                          /* only the alignment of y and z is read; z NULL: no apply kernel asked for */
+  const void* z;
+  int force_scalar;                       /* < 0: the CFM_DWCONV_SCALAR environment switch as the library read it; 0 / 1 */
+} cfm_convmod_query;
+typedef struct {
+  int family;                             /* cfm_convmod_family of the depthwise kernel of `op` */
+  int dz16;                               /* folded vectorised backward: 1 when dz is staged as bf16 */
+  int apply;                              /* cfm_convmod_apply */
+} cfm_convmod_choice;
+/* The selection the launchers themselves make (they call the same routine); calls no GPU API.  Returns CFM_OK with
+   family UNSUPPORTED for a kernel size no kernel of `op` exists for, CFM_ERR_ARG for a null pointer or an unknown op. */
+int cfm_convmod_plan(const cfm_convmod_query* q, cfm_convmod_choice* out);
+
 /* ---------------------------------------------------------------- Attention
  * nn.MultiheadAttention(need_weights=False, key_padding_mask) core (torchaudio ConformerLayer
  * self_attn), optionally with Transformer-XL relative positions (transformers

@@ -86,6 +86,10 @@ GEMM_SEL_AUTO, GEMM_SEL_PIPE256, GEMM_SEL_PIPE256S, GEMM_SEL_192, GEMM_SEL_PIPE1
 (GEMM_EPI_GENERIC, GEMM_EPI_BF16, GEMM_EPI_BF16_BIAS, GEMM_EPI_BF16_SILU, GEMM_EPI_BF16_ACTG, GEMM_EPI_BF16_RD,
  GEMM_EPI_F32, GEMM_EPI_F32_RES, GEMM_EPI_BF16_SILU_MX, GEMM_EPI_BF16_RES, GEMM_EPI_F32R_BF16,
  GEMM_EPI_BF16_DELTA) = range(12)
+# cfm_convmod_op / cfm_convmod_family / cfm_convmod_apply (cfm_convmod_plan)
+CONVMOD_OP_FWD, CONVMOD_OP_BWD, CONVMOD_OP_BWD_BN, CONVMOD_OP_BWD_GN = range(4)
+CONVMOD_FAM_UNSUPPORTED, CONVMOD_FAM_VEC, CONVMOD_FAM_SCALAR_KT, CONVMOD_FAM_SCALAR_KRT = range(4)
+CONVMOD_APPLY_NONE, CONVMOD_APPLY_SCALAR, CONVMOD_APPLY_VEC8 = range(3)
 # cfm_attn_mode (cfm_attn_set_mode)
 ATTN_MODE_TILED = 1 << 0
 ATTN_MODE_STAGING_ONLY = 1 << 1
@@ -95,6 +99,18 @@ ATTN_MODE_REL_ZERO_FILL = 1 << 6
 ATTN_MODE_REL_DPOS_R4 = 1 << 7
 ATTN_MODE_REL_DQ_RECOMPUTE = 1 << 9
 ATTN_MODE_DQ_RECOMPUTE = 1 << 10
+
+
+class ConvmodQuery(ctypes.Structure):
+    """cfm_convmod_query (include/cfm.h): one conv-module launch as cfm_convmod_plan reads it."""
+    _fields_ = [("op", c_int), ("norm", c_int), ("dtype_a", c_int), ("dtype_da", c_int), ("dtype_dz", c_int),
+                ("dtype_z", c_int), ("M", c_long), ("C", c_int), ("K", c_int), ("y", c_void_p), ("z", c_void_p),
+                ("force_scalar", c_int)]
+
+
+class ConvmodChoice(ctypes.Structure):
+    """cfm_convmod_choice (include/cfm.h)."""
+    _fields_ = [("family", c_int), ("dz16", c_int), ("apply", c_int)]
 
 
 class FfoldGeo(ctypes.Structure):
@@ -183,6 +199,7 @@ _SIGS = {
                                   c_void_p]),
     "cfm_convmod_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "cfm_convmod_nparts": (c_long, [c_int, c_int]),
+    "cfm_convmod_plan": (c_int, [c_void_p, c_void_p]),
     "cfm_glu_dwconv_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                    c_void_p, c_void_p]),
     "cfm_bn_silu_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int,

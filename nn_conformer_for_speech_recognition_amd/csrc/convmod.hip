@@ -368,6 +368,33 @@ __global__ __launch_bounds__(256) void bn_bwd_rows_kernel(const void* __restrict
   }
 }
 
+// One element of the BatchNorm / GroupNorm (+ SiLU) input gradient, in the one operation order every kernel that
+// forms it uses -- the unfused apply kernels here, the scalar folded depthwise backward and, on packed pairs, the
+// vectorised one -- so a folded launch and the unfused pair hand the depthwise backward the same fp32 dy bit for
+// bit (written with explicit fmaf: nothing is left to contraction).  sgr = silu'(pre) = s (1 + pre (1 - s)).
+//   BatchNorm: is = invstd, nmi = -mean invstd, gi = gamma invstd, k1 = dbeta / M, k2 = dgamma / M (eval: 0, 0)
+//     dy = gi ((du - yhat k2) - k1)
+//   GroupNorm: gis = rstd[b], gnm = -mean[b] rstd[b], gi = gamma rstd[b], bbt = beta + gnm gamma,
+//     gk1 = -rstd[b] k1[b], gk2 = -rstd[b] k2[b];  dy = gi du + (yhat gk2 + gk1)
+__device__ __forceinline__ float bn_dy_elem(float y, float dz, float is, float nmi, float g, float bt, float gi,
+                                            float k1, float k2, bool act = true) {
+  const float yh = fmaf(y, is, nmi);
+  float du = dz;
+  if (act) {
+    const float pre = fmaf(yh, g, bt);
+    const float s = sigmoid_f(pre);
+    du = dz * fmaf(s, pre * (1.f - s), s);
+  }
+  return gi * (fmaf(-yh, k2, du) - k1);
+}
+__device__ __forceinline__ float gn_dy_elem(float y, float dz, float gis, float gnm, float gi, float bbt, float gk1,
+                                            float gk2) {
+  const float yh = fmaf(y, gis, gnm);
+  const float pre = fmaf(y, gi, bbt);
+  const float s = sigmoid_f(pre);
+  return fmaf(gi, dz * fmaf(s, pre * (1.f - s), s), fmaf(yh, gk2, gk1));
+}
+
 __global__ void bn_bwd_apply_kernel(const void* __restrict__ dz, int dtdz, const float* __restrict__ y,
                                     const float* __restrict__ gamma, const float* __restrict__ beta,
                                     const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -378,11 +405,8 @@ __global__ void bn_bwd_apply_kernel(const void* __restrict__ dz, int dtdz, const
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const int c = (int)(i % C);
     const float is = invstd[c], g = gamma[c];
-    const float yh = (y[i] - mean[c]) * is;
-    const float du = ld_dyn(dz, dtdz, i) * (act ? silu_grad_f(yh * g + beta[c]) : 1.f);
-    float v = du;
-    if (training) v = du - dbeta[c] * invM - yh * dgamma[c] * invM;
-    dy[i] = g * is * v;
+    const float k1 = training ? dbeta[c] * invM : 0.f, k2 = training ? dgamma[c] * invM : 0.f;
+    dy[i] = bn_dy_elem(y[i], ld_dyn(dz, dtdz, i), is, -mean[c] * is, g, beta[c], g * is, k1, k2, act != 0);
   }
 }
 
@@ -396,9 +420,8 @@ __global__ void bn_bwd_apply_total_kernel(const void* __restrict__ dz, int dtdz,
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const int c = (int)(i % C);
     const float is = invstd[c], g = gamma[c];
-    const float yh = (y[i] - mean[c]) * is;
-    const float du = ld_dyn(dz, dtdz, i) * silu_grad_f(yh * g + beta[c]);
-    dy[i] = g * is * (du - dbeta[c] * invM - yh * dgamma[c] * invM);
+    dy[i] = bn_dy_elem(y[i], ld_dyn(dz, dtdz, i), is, -mean[c] * is, g, beta[c], g * is, dbeta[c] * invM,
+                       dgamma[c] * invM);
   }
 }
 
@@ -550,10 +573,9 @@ __global__ void gn_bwd_apply_kernel(const void* __restrict__ dz, int dtdz, const
   const long tc = (long)T * C, n = tc * B;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const int c = (int)(i % C), b = (int)(i / tc);
-    const float rs = rstd[b], g = gamma[c];
-    const float yh = (y[i] - mean[b]) * rs;
-    const float du = ld_dyn(dz, dtdz, i) * silu_grad_f(yh * g + beta[c]);
-    dy[i] = rs * (g * du - coef[2 * b] - yh * coef[2 * b + 1]);
+    const float rs = rstd[b], g = gamma[c], nm = -mean[b] * rs;
+    dy[i] = gn_dy_elem(y[i], ld_dyn(dz, dtdz, i), rs, nm, g * rs, fmaf(nm, g, beta[c]), -rs * coef[2 * b],
+                       -rs * coef[2 * b + 1]);
   }
 }
 
@@ -598,28 +620,26 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_kernel(const float* __rest
     const TA* ap = reinterpret_cast<const TA*>(a) + cc;
     float dv[NR], xv[NR], gv[NR];
     float bg = 0.f, bis = 0.f, bmu = 0.f, bbt = 0.f, bk1 = 0.f, bk2 = 0.f;
+    // the operands of bn_dy_elem / gn_dy_elem: bmu = -mean invstd; GN: bbt = beta + bmu gamma, bk = -rstd k
     if constexpr (BN) {
-      bg = bn.gamma[cc]; bis = bn.invstd[cc]; bmu = bn.mean[cc]; bbt = bn.beta[cc];
+      bg = bn.gamma[cc]; bis = bn.invstd[cc]; bmu = -bn.mean[cc] * bis; bbt = bn.beta[cc];
       bk1 = bn.training ? bn.dbeta[cc] * bn.invM : 0.f;
       bk2 = bn.training ? bn.dgamma[cc] * bn.invM : 0.f;
     }
     if constexpr (GN) {
-      bg = bn.gamma[cc]; bis = bn.invstd[b]; bmu = bn.mean[b]; bbt = bn.beta[cc];
-      bk1 = bn.coef[2 * b];
-      bk2 = bn.coef[2 * b + 1];
+      bg = bn.gamma[cc]; bis = bn.invstd[b]; bmu = -bn.mean[b] * bis; bbt = fmaf(bmu, bg, bn.beta[cc]);
+      bk1 = -bis * bn.coef[2 * b];
+      bk2 = -bis * bn.coef[2 * b + 1];
     }
 #pragma unroll
     for (int i = 0; i < NR; ++i) {
       const int t = min(max(t0 - pad + wv + 4 * i, 0), T - 1);
       const long row = (long)b * T + t;
       if constexpr (BN) {
-        const float yh = (bn.y[row * C + cc] - bmu) * bis;
-        const float du = ld_dyn(bn.dz, bn.dtdz, row * C + cc) * silu_grad_f(yh * bg + bbt);
-        dv[i] = bg * bis * (du - bk1 - yh * bk2);
+        dv[i] = bn_dy_elem(bn.y[row * C + cc], ld_dyn(bn.dz, bn.dtdz, row * C + cc), bis, bmu, bg, bbt, bg * bis, bk1,
+                           bk2);
       } else if constexpr (GN) {
-        const float yh = (bn.y[row * C + cc] - bmu) * bis;
-        const float du = ld_dyn(bn.dz, bn.dtdz, row * C + cc) * silu_grad_f(yh * bg + bbt);
-        dv[i] = bis * (bg * du - bk1 - yh * bk2);
+        dv[i] = gn_dy_elem(bn.y[row * C + cc], ld_dyn(bn.dz, bn.dtdz, row * C + cc), bis, bmu, bg * bis, bbt, bk1, bk2);
       } else {
         dv[i] = dy[row * C + cc];
       }
@@ -827,7 +847,8 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_vec_kernel(const float* __
   }
   // per-element BN + SiLU backward and GLU on packed FP32 pairs (v_pk_fma / v_pk_mul / v_pk_add: the transcendental
   // exp / rcp stay scalar); the gate sigmoid of the tile's own rows is kept for the da stores (sg4: computed once --
-  // the stores recomputed it); same operations per element as the scalar form, up to FMA contraction
+  // the stores recomputed it); the operations and their order are bn_dy_elem's / gn_dy_elem's, so dy is bit-identical
+  // to the scalar kernels' (tests/test_gpu_convmod.py holds the folded launch to the unfused pair)
   typedef float f2 __attribute__((ext_vector_type(2)));
   f2 gi2[2], nmi2[2], bg2[2], bbt2[2], bk1_2[2], bk2_2[2];
   if constexpr (BN) {
@@ -991,11 +1012,17 @@ int ew_grid(long n) {
   return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
 }
 
+// the apply kernel of n = M * C elements (BatchNorm and GroupNorm alike): 8 per thread where every group of 8
+// shares a row and both arrays take 16-byte accesses, else the grid-stride kernel
+int apply_kind(const void* y, const void* z, int dtz, long n, int C) {
+  const bool vec = C % 8 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)z & 15) == 0 &&
+                   (dtz == CFM_BF16 || dtz == CFM_F32) && n / 8 / 256 < (1L << 31);
+  return vec ? CFM_CONVMOD_APPLY_VEC8 : CFM_CONVMOD_APPLY_SCALAR;
+}
+
 void bn_apply(const float* y, const float* gamma, const float* beta, const float* mean, const float* invstd, void* z,
               int dtz, long M, int C, int act, hipStream_t s) {
-  const bool vec = C % 8 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)z & 15) == 0 &&
-                   (dtz == CFM_BF16 || dtz == CFM_F32) && M * C / 8 / 256 < (1L << 31);
-  if (vec) {
+  if (apply_kind(y, z, dtz, M * C, C) == CFM_CONVMOD_APPLY_VEC8) {
     const unsigned nb = (unsigned)((M * C / 8 + 255) / 256);
     if (dtz == CFM_BF16)
       hipLaunchKernelGGL(bn_apply_vec8<CFM_BF16>, dim3(nb), dim3(256), 0, s, y, gamma, beta, mean, invstd, z, M, C, act);
@@ -1030,7 +1057,40 @@ int bn_bwd_impl(const void* dz, int dtdz, const float* y, const float* gamma, co
 
 #define CFM_K_CASES(X) X(3) X(5) X(7) X(15) X(31) X(33)
 bool g_dwconv_scalar = getenv("CFM_DWCONV_SCALAR") != nullptr;   // A/B: the one-channel-per-lane kernels
+
+bool k_compiled(int K) {
+  switch (K) {
+#define X(k) case k:
+    CFM_K_CASES(X)
+#undef X
+    return true;
+    default: return false;
+  }
+}
+
+// The one selection rule of the depthwise kernels (cfm_convmod_plan reports it, every launcher below acts on it):
+// vectorised for bf16 a (backward: and bf16 da), C % 4 == 0 and a compiled K unless the scalar switch is set; else
+// one channel per lane with K compiled where it is; else K at run time, which the folded backwards do not have.
+int dwconv_family(int op, int dta, int dtda, int C, int K, bool scalar) {
+  if (K < 1 || K > KMAX || (K % 2) != 1) return CFM_CONVMOD_FAM_UNSUPPORTED;
+  const bool kc = k_compiled(K);
+  const bool bf = dta == CFM_BF16 && (op == CFM_CONVMOD_OP_FWD || dtda == CFM_BF16);
+  if (!scalar && bf && (C % 4) == 0 && kc) return CFM_CONVMOD_FAM_VEC;
+  if (kc) return CFM_CONVMOD_FAM_SCALAR_KT;
+  return op == CFM_CONVMOD_OP_FWD || op == CFM_CONVMOD_OP_BWD ? CFM_CONVMOD_FAM_SCALAR_KRT : CFM_CONVMOD_FAM_UNSUPPORTED;
+}
 }  // namespace
+
+CFM_EXPORT int cfm_convmod_plan(const cfm_convmod_query* q, cfm_convmod_choice* out) {
+  CFM_REQUIRE(q && out, CFM_ERR_ARG, "null pointer");
+  CFM_REQUIRE(q->op >= CFM_CONVMOD_OP_FWD && q->op <= CFM_CONVMOD_OP_BWD_GN, CFM_ERR_ARG, "unknown op");
+  const bool scalar = q->force_scalar < 0 ? g_dwconv_scalar : q->force_scalar != 0;
+  out->family = dwconv_family(q->op, q->dtype_a, q->dtype_da, q->C, q->K, scalar);
+  const bool folded = q->op == CFM_CONVMOD_OP_BWD_BN || q->op == CFM_CONVMOD_OP_BWD_GN;
+  out->dz16 = out->family == CFM_CONVMOD_FAM_VEC && folded && q->dtype_dz == CFM_BF16;
+  out->apply = q->z ? apply_kind(q->y, q->z, q->dtype_z, q->M * q->C, q->C) : CFM_CONVMOD_APPLY_NONE;
+  return CFM_OK;
+}
 
 CFM_EXPORT size_t cfm_convmod_ws_bytes(int B, int T, int C, int K) {
   const long np = conv_nparts(B, T);
@@ -1055,7 +1115,7 @@ CFM_EXPORT int cfm_glu_dwconv_fwd(const void* a, int dta, const float* w, const 
   dim3 grid(cdiv(C, CT), cdiv(T, TT), B);
   const size_t lds = (size_t)(TT + K - 1) * CT * sizeof(float);
   hipStream_t s = cfm::as_stream(stream);
-  if (dta == CFM_BF16 && (C % 4) == 0 && !g_dwconv_scalar) {
+  if (dwconv_family(CFM_CONVMOD_OP_FWD, dta, dta, C, K, g_dwconv_scalar) == CFM_CONVMOD_FAM_VEC) {
     switch (K) {
 #define X(k) case k: hipLaunchKernelGGL((glu_dwconv_fwd_vec_kernel<k>), grid, dim3(256), 0, s, reinterpret_cast<const bf16*>(a), w, bias, y, T, C, ws); \
                      return cfm::check_launch("cfm_glu_dwconv_fwd");
@@ -1138,10 +1198,11 @@ CFM_EXPORT int cfm_bn_bwd(const void* dz, int dtdz, const float* y, const float*
 
 namespace {
 
-// the vectorised backward for bf16 a/da, C % 4 == 0 and a compiled K; false if not eligible
+// the vectorised backward where dwconv_family selects it; false if not
 bool dwconv_bwd_vec(const float* dy, const void* a, int dta, const float* w, void* da, int dtda, int B, int T, int C,
                     int K, float* ws, const BnBwd& bn, bool use_bn, hipStream_t s, bool use_gn = false) {
-  if (g_dwconv_scalar || dta != CFM_BF16 || dtda != CFM_BF16 || (C % 4) != 0) return false;
+  const int op = use_bn ? CFM_CONVMOD_OP_BWD_BN : use_gn ? CFM_CONVMOD_OP_BWD_GN : CFM_CONVMOD_OP_BWD;
+  if (dwconv_family(op, dta, dtda, C, K, g_dwconv_scalar) != CFM_CONVMOD_FAM_VEC) return false;
   const bool dz16 = (use_bn || use_gn) && bn.dtdz == CFM_BF16;
   dim3 grid(cdiv(C, CT), cdiv(T, TT), B);
   const bf16* ab = reinterpret_cast<const bf16*>(a);
@@ -1248,9 +1309,7 @@ CFM_EXPORT int cfm_gn_silu_fwd(const float* y, const float* gamma, const float* 
   const long np = conv_nparts(B, T), n = (long)B * T * C;
   hipLaunchKernelGGL(gn_sample_kernel<false>, dim3(B), dim3(1024), 0, s, ws, ws + np * C, nt, C, nullptr,
                      1.0 / ((double)T * C), eps, mean, rstd);
-  const bool vec = C % 8 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)z & 15) == 0 &&
-                   (dtz == CFM_BF16 || dtz == CFM_F32) && n / 8 / 256 < (1L << 31);
-  if (vec) {
+  if (apply_kind(y, z, dtz, n, C) == CFM_CONVMOD_APPLY_VEC8) {
     const unsigned nb = (unsigned)((n / 8 + 255) / 256);
     if (dtz == CFM_BF16)
       hipLaunchKernelGGL(gn_apply_vec8<CFM_BF16>, dim3(nb), dim3(256), 0, s, y, gamma, beta, mean, rstd, z, B, T, C);
