@@ -376,52 +376,53 @@ __global__ __launch_bounds__(256) void bn_bwd_rows_kernel(const void* __restrict
 //     dy = gi ((du - yhat k2) - k1)
 //   GroupNorm: gis = rstd[b], gnm = -mean[b] rstd[b], gi = gamma rstd[b], bbt = beta + gnm gamma,
 //     gk1 = -rstd[b] k1[b], gk2 = -rstd[b] k2[b];  dy = gi du + (yhat gk2 + gk1)
-__device__ __forceinline__ float bn_dy_elem(float y, float dz, float is, float nmi, float g, float bt, float gi,
-                                            float k1, float k2, bool act = true) {
-  const float yh = fmaf(y, is, nmi);
+// bn_dy_ops / gn_dy_ops derive those operands for one channel (GroupNorm: of sample b); the unfused apply kernels and
+// the scalar folded kernel take them from here, the vectorised kernel forms the same values on packed pairs.
+struct BnDy { float is, nmi, g, bt, gi, k1, k2; };
+struct GnDy { float gis, gnm, gi, bbt, gk1, gk2; };
+
+__device__ __forceinline__ BnDy bn_dy_ops(const float* gamma, const float* beta, const float* mean,
+                                          const float* invstd, const float* dgamma, const float* dbeta, float invM,
+                                          int training, int c) {
+  const float g = gamma[c], is = invstd[c];
+  return {is, -mean[c] * is, g, beta[c], g * is, training ? dbeta[c] * invM : 0.f, training ? dgamma[c] * invM : 0.f};
+}
+__device__ __forceinline__ GnDy gn_dy_ops(const float* gamma, const float* beta, const float* mean, const float* rstd,
+                                          const float* coef, int b, int c) {
+  const float g = gamma[c], rs = rstd[b], nm = -mean[b] * rs;
+  const float bbt = fmaf(nm, g, beta[c]), gk1 = -rs * coef[2 * b], gk2 = -rs * coef[2 * b + 1];
+  return {rs, nm, g * rs, bbt, gk1, gk2};
+}
+
+__device__ __forceinline__ float bn_dy_elem(float y, float dz, const BnDy& o, bool act = true) {
+  const float yh = fmaf(y, o.is, o.nmi);
   float du = dz;
   if (act) {
-    const float pre = fmaf(yh, g, bt);
+    const float pre = fmaf(yh, o.g, o.bt);
     const float s = sigmoid_f(pre);
     du = dz * fmaf(s, pre * (1.f - s), s);
   }
-  return gi * (fmaf(-yh, k2, du) - k1);
+  return o.gi * (fmaf(-yh, o.k2, du) - o.k1);
 }
-__device__ __forceinline__ float gn_dy_elem(float y, float dz, float gis, float gnm, float gi, float bbt, float gk1,
-                                            float gk2) {
-  const float yh = fmaf(y, gis, gnm);
-  const float pre = fmaf(y, gi, bbt);
+__device__ __forceinline__ float gn_dy_elem(float y, float dz, const GnDy& o) {
+  const float yh = fmaf(y, o.gis, o.gnm);
+  const float pre = fmaf(y, o.gi, o.bbt);
   const float s = sigmoid_f(pre);
-  return fmaf(gi, dz * fmaf(s, pre * (1.f - s), s), fmaf(yh, gk2, gk1));
+  return fmaf(o.gi, dz * fmaf(s, pre * (1.f - s), s), fmaf(yh, o.gk2, o.gk1));
 }
 
+// Msum: the rows dgamma / dbeta were summed over -- M, or under SyncBatchNorm the M_total rows of all replicas
 __global__ void bn_bwd_apply_kernel(const void* __restrict__ dz, int dtdz, const float* __restrict__ y,
                                     const float* __restrict__ gamma, const float* __restrict__ beta,
                                     const float* __restrict__ mean, const float* __restrict__ invstd,
                                     const float* __restrict__ dgamma, const float* __restrict__ dbeta, int training,
-                                    float* __restrict__ dy, long M, int C, int act) {
+                                    float* __restrict__ dy, long M, int C, int act, long Msum) {
   const long n = M * C;
-  const float invM = 1.f / (float)M;
+  const float invM = 1.f / (float)Msum;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const int c = (int)(i % C);
-    const float is = invstd[c], g = gamma[c];
-    const float k1 = training ? dbeta[c] * invM : 0.f, k2 = training ? dgamma[c] * invM : 0.f;
-    dy[i] = bn_dy_elem(y[i], ld_dyn(dz, dtdz, i), is, -mean[c] * is, g, beta[c], g * is, k1, k2, act != 0);
-  }
-}
-
-// SyncBatchNorm input gradient: the sums are over M_total rows of all replicas (invM = 1 / M_total)
-__global__ void bn_bwd_apply_total_kernel(const void* __restrict__ dz, int dtdz, const float* __restrict__ y,
-                                          const float* __restrict__ gamma, const float* __restrict__ beta,
-                                          const float* __restrict__ mean, const float* __restrict__ invstd,
-                                          const float* __restrict__ dgamma, const float* __restrict__ dbeta,
-                                          float* __restrict__ dy, long M, int C, float invM) {
-  const long n = M * C;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C);
-    const float is = invstd[c], g = gamma[c];
-    dy[i] = bn_dy_elem(y[i], ld_dyn(dz, dtdz, i), is, -mean[c] * is, g, beta[c], g * is, dbeta[c] * invM,
-                       dgamma[c] * invM);
+    const BnDy o = bn_dy_ops(gamma, beta, mean, invstd, dgamma, dbeta, invM, training, c);
+    dy[i] = bn_dy_elem(y[i], ld_dyn(dz, dtdz, i), o, act != 0);
   }
 }
 
@@ -573,18 +574,20 @@ __global__ void gn_bwd_apply_kernel(const void* __restrict__ dz, int dtdz, const
   const long tc = (long)T * C, n = tc * B;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const int c = (int)(i % C), b = (int)(i / tc);
-    const float rs = rstd[b], g = gamma[c], nm = -mean[b] * rs;
-    dy[i] = gn_dy_elem(y[i], ld_dyn(dz, dtdz, i), rs, nm, g * rs, fmaf(nm, g, beta[c]), -rs * coef[2 * b],
-                       -rs * coef[2 * b + 1]);
+    const GnDy o = gn_dy_ops(gamma, beta, mean, rstd, coef, b, c);
+    dy[i] = gn_dy_elem(y[i], ld_dyn(dz, dtdz, i), o);
   }
 }
 
-// BatchNorm1d + SiLU backward folded into the depthwise-conv backward (BN=true): the kernel reads dz (the
+// what a depthwise backward kernel stages as dy: the dy array, or a norm's input gradient formed from y and dz
+enum class Norm { NONE, BN, GN };
+
+// BatchNorm1d + SiLU backward folded into the depthwise-conv backward (Norm::BN): the kernel reads dz (the
 // pointwise-conv-2 data gradient) and the BN input y and forms the BN input gradient
 //   dy = gamma * invstd * (du - dbeta / M - yhat * dgamma / M)   (train; eval: gamma * invstd * du)
 //   du = dz * silu'(yhat * gamma + beta),  yhat = (y - mean) * invstd
 // on the fly, so the fp32 dy never goes through HBM (one write + one read of B*T*C floats and a launch saved).
-// GN=true folds the GroupNorm(1, C) + SiLU backward the same way: mean / invstd are per sample (B each), coef is the
+// Norm::GN folds the GroupNorm(1, C) + SiLU backward the same way: mean / invstd are per sample (B each), coef is the
 // (B, 2) buffer of (k1, k2) from cfm_gn_silu_bwd_sums, and
 //   dy = rstd[b] * (gamma[c] * du - k1[b] - yhat * k2[b]),  yhat = (y - mean[b]) * rstd[b]
 // (dgamma, dbeta, invM and training are not read).
@@ -599,7 +602,7 @@ struct BnBwd {
 
 // backward of y = dwconv(GLU(a)).  grid (ceil(C/CT), ceil(T/TT), B)
 // part: [nparts][K+1][C] per-block partial dw (K taps) and db (tap K).
-template <int KT, typename TA, bool BN = false, bool GN = false>
+template <int KT, typename TA, Norm NM = Norm::NONE>
 __global__ __launch_bounds__(256) void glu_dwconv_bwd_kernel(const float* __restrict__ dy,
                                                              const void* __restrict__ a, int dta,
                                                              const float* __restrict__ w, void* __restrict__ da,
@@ -619,27 +622,19 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_kernel(const float* __rest
     const int cc = c < C ? c : C - 1;
     const TA* ap = reinterpret_cast<const TA*>(a) + cc;
     float dv[NR], xv[NR], gv[NR];
-    float bg = 0.f, bis = 0.f, bmu = 0.f, bbt = 0.f, bk1 = 0.f, bk2 = 0.f;
-    // the operands of bn_dy_elem / gn_dy_elem: bmu = -mean invstd; GN: bbt = beta + bmu gamma, bk = -rstd k
-    if constexpr (BN) {
-      bg = bn.gamma[cc]; bis = bn.invstd[cc]; bmu = -bn.mean[cc] * bis; bbt = bn.beta[cc];
-      bk1 = bn.training ? bn.dbeta[cc] * bn.invM : 0.f;
-      bk2 = bn.training ? bn.dgamma[cc] * bn.invM : 0.f;
-    }
-    if constexpr (GN) {
-      bg = bn.gamma[cc]; bis = bn.invstd[b]; bmu = -bn.mean[b] * bis; bbt = fmaf(bmu, bg, bn.beta[cc]);
-      bk1 = -bis * bn.coef[2 * b];
-      bk2 = -bis * bn.coef[2 * b + 1];
-    }
+    BnDy bo{};
+    GnDy go{};
+    if constexpr (NM == Norm::BN)
+      bo = bn_dy_ops(bn.gamma, bn.beta, bn.mean, bn.invstd, bn.dgamma, bn.dbeta, bn.invM, bn.training, cc);
+    if constexpr (NM == Norm::GN) go = gn_dy_ops(bn.gamma, bn.beta, bn.mean, bn.invstd, bn.coef, b, cc);
 #pragma unroll
     for (int i = 0; i < NR; ++i) {
       const int t = min(max(t0 - pad + wv + 4 * i, 0), T - 1);
       const long row = (long)b * T + t;
-      if constexpr (BN) {
-        dv[i] = bn_dy_elem(bn.y[row * C + cc], ld_dyn(bn.dz, bn.dtdz, row * C + cc), bis, bmu, bg, bbt, bg * bis, bk1,
-                           bk2);
-      } else if constexpr (GN) {
-        dv[i] = gn_dy_elem(bn.y[row * C + cc], ld_dyn(bn.dz, bn.dtdz, row * C + cc), bis, bmu, bg * bis, bbt, bk1, bk2);
+      if constexpr (NM == Norm::BN) {
+        dv[i] = bn_dy_elem(bn.y[row * C + cc], ld_dyn(bn.dz, bn.dtdz, row * C + cc), bo);
+      } else if constexpr (NM == Norm::GN) {
+        dv[i] = gn_dy_elem(bn.y[row * C + cc], ld_dyn(bn.dz, bn.dtdz, row * C + cc), go);
       } else {
         dv[i] = dy[row * C + cc];
       }
@@ -656,7 +651,7 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_kernel(const float* __rest
       }
     }
   } else {
-    static_assert(!(BN || GN) || KT > 0, "BN / GN folding: compiled kernel sizes only");
+    static_assert(NM == Norm::NONE || KT > 0, "BN / GN folding: compiled kernel sizes only");
     for (int r = wv; r < rows; r += 4) {
       const int t = t0 - pad + r;
       float vd = 0.f, vg = 0.f;
@@ -774,12 +769,12 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_kernel(const float* __rest
 // depthwise math stays lane = channel out of LDS.  The GLU-input gradient goes back through LDS so the lane that
 // staged a row's GLU inputs also writes that row's da from its registers (no second read of a).
 // Staging map: thread = (row group rs = tid / 16, channel quad q = tid % 16); pass p covers rows rs + 16 p.
-template <int KT, bool BN, bool DZ16, bool GN = false>
+template <int KT, Norm NM, bool DZ16>
 __global__ __launch_bounds__(256) void glu_dwconv_bwd_vec_kernel(const float* __restrict__ dy,
                                                                  const bf16* __restrict__ a,
                                                                  const float* __restrict__ w, bf16* __restrict__ da,
                                                                  int T, int C, float* __restrict__ part, BnBwd bn) {
-  static_assert(!(BN && GN), "one norm at a time");
+  constexpr bool BN = NM == Norm::BN, GN = NM == Norm::GN;
   constexpr bool NORM = BN || GN;    // the staging reads y and dz instead of dy
   constexpr int PAD = (KT - 1) / 2, ROWS = TT + KT - 1, NP = (ROWS + 15) / 16;
   constexpr int FB = TT / 4, WN = FB + KT - 1;
@@ -1020,53 +1015,82 @@ int apply_kind(const void* y, const void* z, int dtz, long n, int C) {
   return vec ? CFM_CONVMOD_APPLY_VEC8 : CFM_CONVMOD_APPLY_SCALAR;
 }
 
+// The one apply launch of both norms: the kernels take (y, gamma, beta, mean, invstd | rstd, z[, dtz], tail...); which
+// of them runs is apply_kind's choice, with the vec8 kernel instantiated for z in bf16 and in fp32.
+template <typename... Tail>
+void norm_apply(void (*vec_bf16)(const float*, const float*, const float*, const float*, const float*, void*, Tail...),
+                void (*vec_f32)(const float*, const float*, const float*, const float*, const float*, void*, Tail...),
+                void (*scalar)(const float*, const float*, const float*, const float*, const float*, void*, int,
+                               Tail...),
+                const float* y, const float* gamma, const float* beta, const float* mean, const float* invstd, void* z,
+                int dtz, long n, int C, hipStream_t s, Tail... tail) {
+  if (apply_kind(y, z, dtz, n, C) == CFM_CONVMOD_APPLY_VEC8)
+    hipLaunchKernelGGL(dtz == CFM_BF16 ? vec_bf16 : vec_f32, dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, s, y,
+                       gamma, beta, mean, invstd, z, tail...);
+  else
+    hipLaunchKernelGGL(scalar, dim3(ew_grid(n)), dim3(256), 0, s, y, gamma, beta, mean, invstd, z, dtz, tail...);
+}
+
 void bn_apply(const float* y, const float* gamma, const float* beta, const float* mean, const float* invstd, void* z,
               int dtz, long M, int C, int act, hipStream_t s) {
-  if (apply_kind(y, z, dtz, M * C, C) == CFM_CONVMOD_APPLY_VEC8) {
-    const unsigned nb = (unsigned)((M * C / 8 + 255) / 256);
-    if (dtz == CFM_BF16)
-      hipLaunchKernelGGL(bn_apply_vec8<CFM_BF16>, dim3(nb), dim3(256), 0, s, y, gamma, beta, mean, invstd, z, M, C, act);
-    else
-      hipLaunchKernelGGL(bn_apply_vec8<CFM_F32>, dim3(nb), dim3(256), 0, s, y, gamma, beta, mean, invstd, z, M, C, act);
-    return;
-  }
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(ew_grid(M * C)), dim3(256), 0, s, y, gamma, beta, mean, invstd, z, dtz, M, C,
-                     act);
+  norm_apply(bn_apply_vec8<CFM_BF16>, bn_apply_vec8<CFM_F32>, bn_apply_kernel, y, gamma, beta, mean, invstd, z, dtz,
+             M * C, C, s, M, C, act);
 }
 
 long conv_nparts(int B, int T) { return (long)B * ((T + TT - 1) / TT); }
 
-// fwd stats from [2][nparts][C] partials at ws; scratch (2C) right after them
-void bn_stats_finalize(const float* ws, int nparts, long M, int C, float* mean, float* invstd, float* rm, float* rv,
-                       float mom, float eps, hipStream_t s) {
-  hipLaunchKernelGGL(bn_stats_kernel, dim3(cdiv(C, 64)), dim3(1024), 0, s, ws, ws + (long)nparts * C, nparts, M, C,
-                     mean, invstd, rm, rv, mom, eps);
+// rows per chunk of the BN_PARTS row-chunk partial kernels (bn_stats_rows_kernel, bn_bwd_rows_kernel)
+long bn_rows_per(long M) {
+  const long rows_per = (M + BN_PARTS - 1) / BN_PARTS;
+  return rows_per > 0 ? rows_per : 1;
+}
+
+// mean / invstd of a BatchNorm forward: training, the batch statistics from the [2][nparts][C] partials at ws (and
+// the running-stat update); else the running statistics.  fn: the export, for the message
+int bn_fwd_stats(const char* fn, int training, const float* ws, int nparts, long M, int C, float* mean, float* invstd,
+                 float* rm, float* rv, float mom, float eps, hipStream_t s) {
+  if (training) {
+    hipLaunchKernelGGL(bn_stats_kernel, dim3(cdiv(C, 64)), dim3(1024), 0, s, ws, ws + (long)nparts * C, nparts, M, C,
+                       mean, invstd, rm, rv, mom, eps);
+    return CFM_OK;
+  }
+  if (!(rm && rv)) return cfm::fail(CFM_ERR_ARG, std::string(fn) + ": eval mode needs running stats");
+  hipLaunchKernelGGL(bn_eval_stats_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, rm, rv, C, eps, mean, invstd);
+  return CFM_OK;
+}
+
+// the BatchNorm parameter gradients: row-chunk partials of (sum du, sum du*yhat) into ws, then their column sums
+void bn_bwd_sums(const void* dz, int dtdz, const float* y, const float* gamma, const float* beta, const float* mean,
+                 const float* invstd, int act, float* dgamma, float* dbeta, long M, int C, float* ws, hipStream_t s) {
+  hipLaunchKernelGGL(bn_bwd_rows_kernel, dim3(cdiv(C, 64), BN_PARTS), dim3(256), 0, s, dz, dtdz, y, gamma, beta, mean,
+                     invstd, M, C, bn_rows_per(M), ws, act);
+  cfm::colreduce_pair(ws, ws + (long)BN_PARTS * C, BN_PARTS, C, dbeta, dgamma, s);
 }
 
 int bn_bwd_impl(const void* dz, int dtdz, const float* y, const float* gamma, const float* beta, const float* mean,
                 const float* invstd, int training, int act, float* dy, float* dgamma, float* dbeta, long M, int C,
                 float* ws, hipStream_t s) {
-  const long rows_per = (M + BN_PARTS - 1) / BN_PARTS;
-  hipLaunchKernelGGL(bn_bwd_rows_kernel, dim3(cdiv(C, 64), BN_PARTS), dim3(256), 0, s, dz, dtdz, y, gamma, beta, mean,
-                     invstd, M, C, rows_per > 0 ? rows_per : 1, ws, act);
-  cfm::colreduce_pair(ws, ws + (long)BN_PARTS * C, BN_PARTS, C, dbeta, dgamma, s);
+  bn_bwd_sums(dz, dtdz, y, gamma, beta, mean, invstd, act, dgamma, dbeta, M, C, ws, s);
   hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_grid(M * C)), dim3(256), 0, s, dz, dtdz, y, gamma, beta, mean,
-                     invstd, dgamma, dbeta, training, dy, M, C, act);
+                     invstd, dgamma, dbeta, training, dy, M, C, act, M);
   return CFM_OK;
 }
 
 #define CFM_K_CASES(X) X(3) X(5) X(7) X(15) X(31) X(33)
 bool g_dwconv_scalar = getenv("CFM_DWCONV_SCALAR") != nullptr;   // A/B: the one-channel-per-lane kernels
 
-bool k_compiled(int K) {
+// The one K switch: f(std::integral_constant<int, K>{}) where K has a compiled variant, false where it has none.
+template <typename F>
+bool with_compiled_k(int K, F&& f) {
   switch (K) {
-#define X(k) case k:
+#define X(k) case k: f(std::integral_constant<int, k>{}); return true;
     CFM_K_CASES(X)
 #undef X
-    return true;
     default: return false;
   }
 }
+
+bool k_compiled(int K) { return with_compiled_k(K, [](auto) {}); }
 
 // The one selection rule of the depthwise kernels (cfm_convmod_plan reports it, every launcher below acts on it):
 // vectorised for bf16 a (backward: and bf16 da), C % 4 == 0 and a compiled K unless the scalar switch is set; else
@@ -1115,24 +1139,17 @@ CFM_EXPORT int cfm_glu_dwconv_fwd(const void* a, int dta, const float* w, const 
   dim3 grid(cdiv(C, CT), cdiv(T, TT), B);
   const size_t lds = (size_t)(TT + K - 1) * CT * sizeof(float);
   hipStream_t s = cfm::as_stream(stream);
-  if (dwconv_family(CFM_CONVMOD_OP_FWD, dta, dta, C, K, g_dwconv_scalar) == CFM_CONVMOD_FAM_VEC) {
-    switch (K) {
-#define X(k) case k: hipLaunchKernelGGL((glu_dwconv_fwd_vec_kernel<k>), grid, dim3(256), 0, s, reinterpret_cast<const bf16*>(a), w, bias, y, T, C, ws); \
-                     return cfm::check_launch("cfm_glu_dwconv_fwd");
-      CFM_K_CASES(X)
-#undef X
-      default: break;
-    }
-  }
-  switch (K) {
-#define X(k) case k: if (dta == CFM_BF16) hipLaunchKernelGGL((glu_dwconv_fwd_kernel<k, bf16>), grid, dim3(256), lds, s, a, dta, w, bias, y, T, C, K, ws); \
-                    else hipLaunchKernelGGL((glu_dwconv_fwd_kernel<k, float>), grid, dim3(256), lds, s, a, dta, w, bias, y, T, C, K, ws); break;
-    CFM_K_CASES(X)
-#undef X
-    default:
-      if (dta == CFM_BF16) hipLaunchKernelGGL((glu_dwconv_fwd_kernel<0, bf16>), grid, dim3(256), lds, s, a, dta, w, bias, y, T, C, K, ws);
-      else hipLaunchKernelGGL((glu_dwconv_fwd_kernel<0, float>), grid, dim3(256), lds, s, a, dta, w, bias, y, T, C, K, ws);
-  }
+  auto scalar = [&](auto kt) {     // one channel per lane; kt 0: K at run time
+    constexpr int k = decltype(kt)::value;
+    if (dta == CFM_BF16) hipLaunchKernelGGL((glu_dwconv_fwd_kernel<k, bf16>), grid, dim3(256), lds, s, a, dta, w, bias, y, T, C, K, ws);
+    else hipLaunchKernelGGL((glu_dwconv_fwd_kernel<k, float>), grid, dim3(256), lds, s, a, dta, w, bias, y, T, C, K, ws);
+  };
+  if (dwconv_family(CFM_CONVMOD_OP_FWD, dta, dta, C, K, g_dwconv_scalar) == CFM_CONVMOD_FAM_VEC)
+    with_compiled_k(K, [&](auto kt) {
+      hipLaunchKernelGGL((glu_dwconv_fwd_vec_kernel<decltype(kt)::value>), grid, dim3(256), 0, s,
+                         reinterpret_cast<const bf16*>(a), w, bias, y, T, C, ws);
+    });
+  else if (!with_compiled_k(K, scalar)) scalar(std::integral_constant<int, 0>{});
   return cfm::check_launch("cfm_glu_dwconv_fwd");
 }
 
@@ -1144,14 +1161,10 @@ CFM_EXPORT int cfm_bn_silu_fwd(const float* y, const float* gamma, const float* 
   CFM_REQUIRE(B > 0 && T > 0 && C > 0, CFM_ERR_SHAPE, "bad shape");
   hipStream_t s = cfm::as_stream(stream);
   const long M = (long)B * T;
-  if (training) {
-    CFM_REQUIRE(ws, CFM_ERR_ARG, "training mode needs the partial sums of cfm_glu_dwconv_fwd");
-    bn_stats_finalize(ws, (int)conv_nparts(B, T), M, C, mean, invstd, running_mean, running_var, momentum, eps, s);
-  } else {
-    CFM_REQUIRE(running_mean && running_var, CFM_ERR_ARG, "eval mode needs running stats");
-    hipLaunchKernelGGL(bn_eval_stats_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, running_mean, running_var, C,
-                       eps, mean, invstd);
-  }
+  CFM_REQUIRE(!training || ws, CFM_ERR_ARG, "training mode needs the partial sums of cfm_glu_dwconv_fwd");
+  if (const int rc = bn_fwd_stats("cfm_bn_silu_fwd", training, ws, (int)conv_nparts(B, T), M, C, mean, invstd,
+                                  running_mean, running_var, momentum, eps, s))
+    return rc;
   bn_apply(y, gamma, beta, mean, invstd, z, dtz, M, C, 1, s);
   return cfm::check_launch("cfm_bn_silu_fwd");
 }
@@ -1172,16 +1185,11 @@ CFM_EXPORT int cfm_bn_fwd(const float* y, const float* gamma, const float* beta,
   CFM_REQUIRE(y && gamma && beta && mean && invstd && z && ws, CFM_ERR_ARG, "null pointer");
   CFM_REQUIRE(M > 0 && C > 0, CFM_ERR_SHAPE, "bad shape");
   hipStream_t s = cfm::as_stream(stream);
-  if (training) {
-    const long rows_per = (M + BN_PARTS - 1) / BN_PARTS;
-    hipLaunchKernelGGL(bn_stats_rows_kernel, dim3(cdiv(C, 64), BN_PARTS), dim3(256), 0, s, y, M, C,
-                       rows_per > 0 ? rows_per : 1, ws);
-    bn_stats_finalize(ws, BN_PARTS, M, C, mean, invstd, running_mean, running_var, momentum, eps, s);
-  } else {
-    CFM_REQUIRE(running_mean && running_var, CFM_ERR_ARG, "eval mode needs running stats");
-    hipLaunchKernelGGL(bn_eval_stats_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, running_mean, running_var, C,
-                       eps, mean, invstd);
-  }
+  if (training)
+    hipLaunchKernelGGL(bn_stats_rows_kernel, dim3(cdiv(C, 64), BN_PARTS), dim3(256), 0, s, y, M, C, bn_rows_per(M), ws);
+  if (const int rc = bn_fwd_stats("cfm_bn_fwd", training, ws, BN_PARTS, M, C, mean, invstd, running_mean, running_var,
+                                  momentum, eps, s))
+    return rc;
   bn_apply(y, gamma, beta, mean, invstd, z, dtz, M, C, act, s);
   return cfm::check_launch("cfm_bn_fwd");
 }
@@ -1198,55 +1206,67 @@ CFM_EXPORT int cfm_bn_bwd(const void* dz, int dtdz, const float* y, const float*
 
 namespace {
 
-// the vectorised backward where dwconv_family selects it; false if not
-bool dwconv_bwd_vec(const float* dy, const void* a, int dta, const float* w, void* da, int dtda, int B, int T, int C,
-                    int K, float* ws, const BnBwd& bn, bool use_bn, hipStream_t s, bool use_gn = false) {
-  const int op = use_bn ? CFM_CONVMOD_OP_BWD_BN : use_gn ? CFM_CONVMOD_OP_BWD_GN : CFM_CONVMOD_OP_BWD;
-  if (dwconv_family(op, dta, dtda, C, K, g_dwconv_scalar) != CFM_CONVMOD_FAM_VEC) return false;
-  const bool dz16 = (use_bn || use_gn) && bn.dtdz == CFM_BF16;
+// The one launch of the depthwise backward, plain (dy) or with a norm's backward folded in (bn): the checks every
+// export shares, the grid, the LDS size, and the kernel dwconv_family selects for (NM, dtypes, C, K).  fn: the export,
+// for the messages.  Leaves the weight-gradient partials in ws (dwconv_bwd_finish turns them into dw / db).
+template <Norm NM>
+int dwconv_bwd_launch(const char* fn, const float* dy, const BnBwd& bn, const void* a, int dta, const float* w,
+                      void* da, int dtda, int B, int T, int C, int K, float* ws, hipStream_t s) {
+  auto bad = [fn](int code, const char* msg) { return cfm::fail(code, std::string(fn) + ": " + msg); };
+  if (!(a && w && da && ws)) return bad(CFM_ERR_ARG, "null pointer");
+  if (!(K >= 1 && K <= KMAX && (K % 2) == 1)) return bad(CFM_ERR_UNSUPPORTED, "depthwise kernel must be odd and <= 63");
+  if (!(B > 0 && T > 0 && C > 0)) return bad(CFM_ERR_SHAPE, "bad shape");
+  constexpr int op = NM == Norm::BN ? CFM_CONVMOD_OP_BWD_BN : NM == Norm::GN ? CFM_CONVMOD_OP_BWD_GN : CFM_CONVMOD_OP_BWD;
   dim3 grid(cdiv(C, CT), cdiv(T, TT), B);
-  const bf16* ab = reinterpret_cast<const bf16*>(a);
-  bf16* dab = reinterpret_cast<bf16*>(da);
-  switch (K) {
-#define X(k) case k:                                                                                             \
-    if (use_gn && dz16) hipLaunchKernelGGL((glu_dwconv_bwd_vec_kernel<k, false, true, true>), grid, dim3(256), 0, s, dy, ab, w, dab, T, C, ws, bn); \
-    else if (use_gn) hipLaunchKernelGGL((glu_dwconv_bwd_vec_kernel<k, false, false, true>), grid, dim3(256), 0, s, dy, ab, w, dab, T, C, ws, bn); \
-    else if (!use_bn) hipLaunchKernelGGL((glu_dwconv_bwd_vec_kernel<k, false, false>), grid, dim3(256), 0, s, dy, ab, w, dab, T, C, ws, bn); \
-    else if (dz16) hipLaunchKernelGGL((glu_dwconv_bwd_vec_kernel<k, true, true>), grid, dim3(256), 0, s, dy, ab, w, dab, T, C, ws, bn); \
-    else hipLaunchKernelGGL((glu_dwconv_bwd_vec_kernel<k, true, false>), grid, dim3(256), 0, s, dy, ab, w, dab, T, C, ws, bn); \
-    return true;
-    CFM_K_CASES(X)
-#undef X
-    default: return false;
+  size_t lds = (size_t)2 * (TT + K - 1) * CT * sizeof(float);
+  const size_t red = (size_t)4 * (K + 1) * CT * sizeof(float);
+  if (red > lds) lds = red;
+  auto scalar = [&](auto kt) {     // one channel per lane; kt 0: K at run time
+    constexpr int k = decltype(kt)::value;
+    if (dta == CFM_BF16) hipLaunchKernelGGL((glu_dwconv_bwd_kernel<k, bf16, NM>), grid, dim3(256), lds, s, dy, a, dta, w, da, dtda, T, C, K, ws, bn);
+    else hipLaunchKernelGGL((glu_dwconv_bwd_kernel<k, float, NM>), grid, dim3(256), lds, s, dy, a, dta, w, da, dtda, T, C, K, ws, bn);
+  };
+  auto vec = [&](auto kt) {        // bf16 a / da; a bf16 dz is staged as bf16
+    constexpr int k = decltype(kt)::value;
+    const bf16* ab = reinterpret_cast<const bf16*>(a);
+    bf16* dab = reinterpret_cast<bf16*>(da);
+    if constexpr (NM != Norm::NONE)
+      if (bn.dtdz == CFM_BF16) {
+        hipLaunchKernelGGL((glu_dwconv_bwd_vec_kernel<k, NM, true>), grid, dim3(256), 0, s, dy, ab, w, dab, T, C, ws, bn);
+        return;
+      }
+    hipLaunchKernelGGL((glu_dwconv_bwd_vec_kernel<k, NM, false>), grid, dim3(256), 0, s, dy, ab, w, dab, T, C, ws, bn);
+  };
+  switch (dwconv_family(op, dta, dtda, C, K, g_dwconv_scalar)) {
+    case CFM_CONVMOD_FAM_VEC: with_compiled_k(K, vec); break;
+    case CFM_CONVMOD_FAM_SCALAR_KT: with_compiled_k(K, scalar); break;
+    default:
+      if constexpr (NM == Norm::NONE) scalar(std::integral_constant<int, 0>{});
+      else return bad(CFM_ERR_UNSUPPORTED, "kernel size without a compiled variant");
   }
+  return CFM_OK;
+}
+
+// the weight-gradient tail of every depthwise backward: the [nparts][K+1][C] partials in ws to sums (right after
+// them), sums to dw / db; dw == NULL defers it to cfm_glu_dwconv_bwd_wgrad.  Returns the export's launch status.
+int dwconv_bwd_finish(const char* fn, float* ws, int B, int T, int C, int K, float* dw, float* db, hipStream_t s) {
+  if (dw) {
+    const long np = conv_nparts(B, T);
+    float* sums = ws + np * (long)C * (K + 1);
+    cfm::colreduce(ws, (int)np, (long)C * (K + 1), sums, 0, s);
+    hipLaunchKernelGGL(dwconv_scatter_kernel, dim3(cdiv((long)C * (K + 1), 256)), dim3(256), 0, s, sums, C, K, dw, db);
+  }
+  return cfm::check_launch(fn);
 }
 }  // namespace
 
 CFM_EXPORT int cfm_glu_dwconv_bwd(const float* dy, const void* a, int dta, const float* w, void* da, int dtda,
                                   float* dw, float* db, int B, int T, int C, int K, float* ws, void* stream) {
-  CFM_REQUIRE(dy && a && w && da && ws, CFM_ERR_ARG, "null pointer");
-  CFM_REQUIRE(K >= 1 && K <= KMAX && (K % 2) == 1, CFM_ERR_UNSUPPORTED, "depthwise kernel must be odd and <= 63");
-  CFM_REQUIRE(B > 0 && T > 0 && C > 0, CFM_ERR_SHAPE, "bad shape");
-  dim3 grid(cdiv(C, CT), cdiv(T, TT), B);
-  size_t lds = (size_t)2 * (TT + K - 1) * CT * sizeof(float);
-  const size_t red = (size_t)4 * (K + 1) * CT * sizeof(float);
-  if (red > lds) lds = red;
+  CFM_REQUIRE(dy, CFM_ERR_ARG, "null pointer");
   hipStream_t s = cfm::as_stream(stream);
-  if (!dwconv_bwd_vec(dy, a, dta, w, da, dtda, B, T, C, K, ws, BnBwd{}, false, s)) switch (K) {
-#define X(k) case k: if (dta == CFM_BF16) hipLaunchKernelGGL((glu_dwconv_bwd_kernel<k, bf16>), grid, dim3(256), lds, s, dy, a, dta, w, da, dtda, T, C, K, ws, BnBwd{}); \
-                    else hipLaunchKernelGGL((glu_dwconv_bwd_kernel<k, float>), grid, dim3(256), lds, s, dy, a, dta, w, da, dtda, T, C, K, ws, BnBwd{}); break;
-    CFM_K_CASES(X)
-#undef X
-    default:
-      if (dta == CFM_BF16) hipLaunchKernelGGL((glu_dwconv_bwd_kernel<0, bf16>), grid, dim3(256), lds, s, dy, a, dta, w, da, dtda, T, C, K, ws, BnBwd{});
-      else hipLaunchKernelGGL((glu_dwconv_bwd_kernel<0, float>), grid, dim3(256), lds, s, dy, a, dta, w, da, dtda, T, C, K, ws, BnBwd{});
-  }
-  if (!dw) return cfm::check_launch("cfm_glu_dwconv_bwd");   // weight grads later: cfm_glu_dwconv_bwd_wgrad
-  const long np = conv_nparts(B, T);
-  float* sums = ws + np * (long)C * (K + 1);
-  cfm::colreduce(ws, (int)np, (long)C * (K + 1), sums, 0, s);
-  hipLaunchKernelGGL(dwconv_scatter_kernel, dim3(cdiv((long)C * (K + 1), 256)), dim3(256), 0, s, sums, C, K, dw, db);
-  return cfm::check_launch("cfm_glu_dwconv_bwd");
+  if (const int rc = dwconv_bwd_launch<Norm::NONE>(__func__, dy, BnBwd{}, a, dta, w, da, dtda, B, T, C, K, ws, s))
+    return rc;
+  return dwconv_bwd_finish(__func__, ws, B, T, C, K, dw, db, s);
 }
 
 // the BatchNorm1d + SiLU input gradient folded into the depthwise-conv backward (BnBwd above); dbeta / dgamma are
@@ -1257,30 +1277,13 @@ CFM_EXPORT int cfm_glu_dwconv_bwd_bn(const void* dz, int dtdz, const float* y, c
                                      float invM, int training, const void* a, int dta, const float* w, void* da,
                                      int dtda, float* dw, float* db, int B, int T, int C, int K, float* ws,
                                      void* stream) {
-  CFM_REQUIRE(dz && y && gamma && beta && mean && invstd && a && w && da && ws, CFM_ERR_ARG, "null pointer");
+  CFM_REQUIRE(dz && y && gamma && beta && mean && invstd, CFM_ERR_ARG, "null pointer");
   CFM_REQUIRE(!training || (dbeta && dgamma), CFM_ERR_ARG, "training mode needs dbeta / dgamma");
-  CFM_REQUIRE(K >= 1 && K <= KMAX && (K % 2) == 1, CFM_ERR_UNSUPPORTED, "depthwise kernel must be odd and <= 63");
-  CFM_REQUIRE(B > 0 && T > 0 && C > 0, CFM_ERR_SHAPE, "bad shape");
-  dim3 grid(cdiv(C, CT), cdiv(T, TT), B);
-  size_t lds = (size_t)2 * (TT + K - 1) * CT * sizeof(float);
-  const size_t red = (size_t)4 * (K + 1) * CT * sizeof(float);
-  if (red > lds) lds = red;
   hipStream_t s = cfm::as_stream(stream);
   const BnBwd bn{dz, dtdz, y, gamma, beta, mean, invstd, dgamma, dbeta, invM, training};
-  if (!dwconv_bwd_vec(nullptr, a, dta, w, da, dtda, B, T, C, K, ws, bn, true, s)) switch (K) {
-#define X(k) case k: if (dta == CFM_BF16) hipLaunchKernelGGL((glu_dwconv_bwd_kernel<k, bf16, true>), grid, dim3(256), lds, s, nullptr, a, dta, w, da, dtda, T, C, K, ws, bn); \
-                    else hipLaunchKernelGGL((glu_dwconv_bwd_kernel<k, float, true>), grid, dim3(256), lds, s, nullptr, a, dta, w, da, dtda, T, C, K, ws, bn); break;
-    CFM_K_CASES(X)
-#undef X
-    default:
-      return cfm::fail(CFM_ERR_UNSUPPORTED, "cfm_glu_dwconv_bwd_bn: kernel size without a compiled variant");
-  }
-  if (!dw) return cfm::check_launch("cfm_glu_dwconv_bwd_bn");
-  const long np = conv_nparts(B, T);
-  float* sums = ws + np * (long)C * (K + 1);
-  cfm::colreduce(ws, (int)np, (long)C * (K + 1), sums, 0, s);
-  hipLaunchKernelGGL(dwconv_scatter_kernel, dim3(cdiv((long)C * (K + 1), 256)), dim3(256), 0, s, sums, C, K, dw, db);
-  return cfm::check_launch("cfm_glu_dwconv_bwd_bn");
+  if (const int rc = dwconv_bwd_launch<Norm::BN>(__func__, nullptr, bn, a, dta, w, da, dtda, B, T, C, K, ws, s))
+    return rc;
+  return dwconv_bwd_finish(__func__, ws, B, T, C, K, dw, db, s);
 }
 
 // ----------------------------------------------------------------------------- GroupNorm(1, C) conv module
@@ -1309,16 +1312,8 @@ CFM_EXPORT int cfm_gn_silu_fwd(const float* y, const float* gamma, const float* 
   const long np = conv_nparts(B, T), n = (long)B * T * C;
   hipLaunchKernelGGL(gn_sample_kernel<false>, dim3(B), dim3(1024), 0, s, ws, ws + np * C, nt, C, nullptr,
                      1.0 / ((double)T * C), eps, mean, rstd);
-  if (apply_kind(y, z, dtz, n, C) == CFM_CONVMOD_APPLY_VEC8) {
-    const unsigned nb = (unsigned)((n / 8 + 255) / 256);
-    if (dtz == CFM_BF16)
-      hipLaunchKernelGGL(gn_apply_vec8<CFM_BF16>, dim3(nb), dim3(256), 0, s, y, gamma, beta, mean, rstd, z, B, T, C);
-    else
-      hipLaunchKernelGGL(gn_apply_vec8<CFM_F32>, dim3(nb), dim3(256), 0, s, y, gamma, beta, mean, rstd, z, B, T, C);
-  } else {
-    hipLaunchKernelGGL(gn_apply_kernel, dim3(ew_grid(n)), dim3(256), 0, s, y, gamma, beta, mean, rstd, z, dtz, B, T,
-                       C);
-  }
+  norm_apply(gn_apply_vec8<CFM_BF16>, gn_apply_vec8<CFM_F32>, gn_apply_kernel, y, gamma, beta, mean, rstd, z, dtz, n, C,
+             s, B, T, C);
   return cfm::check_launch("cfm_gn_silu_fwd");
 }
 
@@ -1349,39 +1344,17 @@ CFM_EXPORT int cfm_glu_dwconv_bwd_gn(const void* dz, int dtdz, const float* y, c
                                      const float* mean, const float* rstd, const float* coef, const void* a, int dta,
                                      const float* w, void* da, int dtda, float* dw, float* db, int B, int T, int C,
                                      int K, float* ws, void* stream) {
-  CFM_REQUIRE(dz && y && gamma && beta && mean && rstd && coef && a && w && da && ws, CFM_ERR_ARG, "null pointer");
-  CFM_REQUIRE(K >= 1 && K <= KMAX && (K % 2) == 1, CFM_ERR_UNSUPPORTED, "depthwise kernel must be odd and <= 63");
-  CFM_REQUIRE(B > 0 && T > 0 && C > 0, CFM_ERR_SHAPE, "bad shape");
-  dim3 grid(cdiv(C, CT), cdiv(T, TT), B);
-  size_t lds = (size_t)2 * (TT + K - 1) * CT * sizeof(float);
-  const size_t red = (size_t)4 * (K + 1) * CT * sizeof(float);
-  if (red > lds) lds = red;
+  CFM_REQUIRE(dz && y && gamma && beta && mean && rstd && coef, CFM_ERR_ARG, "null pointer");
   hipStream_t s = cfm::as_stream(stream);
   const BnBwd bn{dz, dtdz, y, gamma, beta, mean, rstd, nullptr, nullptr, 0.f, 1, coef};
-  if (!dwconv_bwd_vec(nullptr, a, dta, w, da, dtda, B, T, C, K, ws, bn, false, s, true)) switch (K) {
-#define X(k) case k: if (dta == CFM_BF16) hipLaunchKernelGGL((glu_dwconv_bwd_kernel<k, bf16, false, true>), grid, dim3(256), lds, s, nullptr, a, dta, w, da, dtda, T, C, K, ws, bn); \
-                    else hipLaunchKernelGGL((glu_dwconv_bwd_kernel<k, float, false, true>), grid, dim3(256), lds, s, nullptr, a, dta, w, da, dtda, T, C, K, ws, bn); break;
-    CFM_K_CASES(X)
-#undef X
-    default:
-      return cfm::fail(CFM_ERR_UNSUPPORTED, "cfm_glu_dwconv_bwd_gn: kernel size without a compiled variant");
-  }
-  if (!dw) return cfm::check_launch("cfm_glu_dwconv_bwd_gn");
-  const long np = conv_nparts(B, T);
-  float* sums = ws + np * (long)C * (K + 1);
-  cfm::colreduce(ws, (int)np, (long)C * (K + 1), sums, 0, s);
-  hipLaunchKernelGGL(dwconv_scatter_kernel, dim3(cdiv((long)C * (K + 1), 256)), dim3(256), 0, s, sums, C, K, dw, db);
-  return cfm::check_launch("cfm_glu_dwconv_bwd_gn");
+  if (const int rc = dwconv_bwd_launch<Norm::GN>(__func__, nullptr, bn, a, dta, w, da, dtda, B, T, C, K, ws, s))
+    return rc;
+  return dwconv_bwd_finish(__func__, ws, B, T, C, K, dw, db, s);
 }
 
 CFM_EXPORT int cfm_glu_dwconv_bwd_wgrad(float* ws, int B, int T, int C, int K, float* dw, float* db, void* stream) {
   CFM_REQUIRE(ws && dw, CFM_ERR_ARG, "null pointer");
-  hipStream_t s = cfm::as_stream(stream);
-  const long np = conv_nparts(B, T);
-  float* sums = ws + np * (long)C * (K + 1);
-  cfm::colreduce(ws, (int)np, (long)C * (K + 1), sums, 0, s);
-  hipLaunchKernelGGL(dwconv_scatter_kernel, dim3(cdiv((long)C * (K + 1), 256)), dim3(256), 0, s, sums, C, K, dw, db);
-  return cfm::check_launch("cfm_glu_dwconv_bwd_wgrad");
+  return dwconv_bwd_finish(__func__, ws, B, T, C, K, dw, db, cfm::as_stream(stream));
 }
 
 // ----------------------------------------------------------------------------- SyncBatchNorm split
@@ -1415,11 +1388,7 @@ CFM_EXPORT int cfm_bn_silu_bwd_sums(const void* dz, int dtdz, const float* y, co
                                     float* dgamma, void* stream) {
   CFM_REQUIRE(dz && y && gamma && beta && mean && invstd && ws && dbeta && dgamma && M > 0 && C > 0, CFM_ERR_ARG,
               "bad args");
-  hipStream_t s = cfm::as_stream(stream);
-  const long rows_per = (M + BN_PARTS - 1) / BN_PARTS;
-  hipLaunchKernelGGL(bn_bwd_rows_kernel, dim3(cdiv(C, 64), BN_PARTS), dim3(256), 0, s, dz, dtdz, y, gamma, beta, mean,
-                     invstd, M, C, rows_per > 0 ? rows_per : 1, ws, 1);
-  cfm::colreduce_pair(ws, ws + (long)BN_PARTS * C, BN_PARTS, C, dbeta, dgamma, s);
+  bn_bwd_sums(dz, dtdz, y, gamma, beta, mean, invstd, 1, dgamma, dbeta, M, C, ws, cfm::as_stream(stream));
   return cfm::check_launch("cfm_bn_silu_bwd_sums");
 }
 
@@ -1428,7 +1397,7 @@ CFM_EXPORT int cfm_bn_silu_bwd_apply(const void* dz, int dtdz, const float* y, c
                                      const float* dgamma_total, long M_total, float* dy, long M, int C, void* stream) {
   CFM_REQUIRE(dz && y && gamma && beta && mean && invstd && dbeta_total && dgamma_total && dy && M_total > 0,
               CFM_ERR_ARG, "bad args");
-  hipLaunchKernelGGL(bn_bwd_apply_total_kernel, dim3(ew_grid(M * C)), dim3(256), 0, cfm::as_stream(stream), dz, dtdz,
-                     y, gamma, beta, mean, invstd, dgamma_total, dbeta_total, dy, M, C, 1.f / (float)M_total);
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_grid(M * C)), dim3(256), 0, cfm::as_stream(stream), dz, dtdz, y,
+                     gamma, beta, mean, invstd, dgamma_total, dbeta_total, 1, dy, M, C, 1, M_total);
   return cfm::check_launch("cfm_bn_silu_bwd_apply");
 }

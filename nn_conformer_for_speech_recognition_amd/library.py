@@ -347,12 +347,8 @@ def conv_glu_dwconv_bn_silu_bwd(dz: Tensor, a: Tensor, y: Tensor, w_dw: Tensor, 
     T = M // B
     a, dz, w_dw = a.contiguous(), dz.contiguous(), w_dw.contiguous()
     ws = ops.convmod_ws(B, T, C, K, a.device)
-    if K in ops.BN_FOLD_K:
-        da, dw, db, dg, dbt = ops.bn_silu_glu_dwconv_bwd(dz, y, gamma, beta, mean, invstd, training, a, w_dw, B, T,
-                                                          C, K, ws, a.dtype)
-    else:
-        dy, dg, dbt = ops.bn_silu_bwd(dz, y, gamma, beta, mean, invstd, training, ws)
-        da, dw, db = ops.glu_dwconv_bwd(dy, a, w_dw, B, T, C, K, ws, a.dtype)
+    da, dw, db, dg, dbt, _ = ops.norm_silu_glu_dwconv_bwd("bn", dz, y, gamma, beta, mean, invstd, training, a, w_dw,
+                                                           B, T, C, K, ws, a.dtype)
     return da, dw, db, dg.clone(), dbt.clone()
 
 
@@ -416,12 +412,8 @@ def conv_glu_dwconv_gn_silu_bwd(dz: Tensor, a: Tensor, y: Tensor, w_dw: Tensor, 
     T = M // B
     a, dz, w_dw = a.contiguous(), dz.contiguous(), w_dw.contiguous()
     ws = ops.convmod_ws(B, T, C, K, a.device)
-    if K in ops.BN_FOLD_K:
-        da, dw, db, dg, dbt = ops.gn_silu_glu_dwconv_bwd(dz, y, gamma, beta, mean, rstd, a, w_dw, B, T, C, K, ws,
-                                                          a.dtype)
-    else:
-        dy, dg, dbt = ops.gn_silu_bwd(dz, y, gamma, beta, mean, rstd, B, T, ws)
-        da, dw, db = ops.glu_dwconv_bwd(dy, a, w_dw, B, T, C, K, ws, a.dtype)
+    da, dw, db, dg, dbt, _ = ops.norm_silu_glu_dwconv_bwd("gn", dz, y, gamma, beta, mean, rstd, True, a, w_dw, B, T, C,
+                                                           K, ws, a.dtype)
     return da, dw, db, dg.clone(), dbt.clone()
 
 

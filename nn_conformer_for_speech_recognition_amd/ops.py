@@ -4,6 +4,7 @@ allocator (so whole steps can be captured into a HIP graph)."""
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 
 import torch
@@ -788,19 +789,40 @@ def bn_silu_bwd(dz, y, gamma, beta, mean, invstd, training, ws):
     return dy, dgamma, dbeta
 
 
-# kernel sizes with a compiled depthwise variant (convmod.hip CFM_K_CASES); the BN-folded backward needs one
-BN_FOLD_K = (3, 5, 7, 15, 31, 33)
+@functools.lru_cache(maxsize=None)
+def dwconv_bwd_folds(K):
+    """Whether kernel size K has a depthwise backward with the norm backward folded in (BatchNorm and GroupNorm
+    alike): cfm_convmod_plan's answer for op BWD_BN, any family but UNSUPPORTED.  The compiled sizes are listed in
+    one place, convmod.hip; cached per K, so no step calls the plan."""
+    q = L.ConvmodQuery(op=L.CONVMOD_OP_BWD_BN, dtype_a=F32, dtype_da=F32, dtype_dz=F32, C=64, K=int(K))
+    c = L.ConvmodChoice()
+    L.call("cfm_convmod_plan", ctypes.byref(q), ctypes.byref(c))
+    return c.family != L.CONVMOD_FAM_UNSUPPORTED
 
 
-def glu_dwconv_bwd(dy, a, w_dw, B, T, C, K, ws, da_dtype, side=None):
-    """side: optional conformer._Side -- the depthwise weight/bias reduction then runs there."""
+def _dwconv_bwd(name, head, a, w_dw, B, T, C, K, ws, da_dtype, side):
+    """One depthwise backward export (cfm_glu_dwconv_bwd, _bn or _gn; head: the arguments it takes before a).
+    side: optional conformer._Side -- the depthwise weight/bias reduction is then left out of the call and runs
+    there.  Returns (da, dw_dw, db_dw)."""
     da = torch.empty(B * T, 2 * C, device=a.device, dtype=da_dtype)
     dw = torch.empty(C, K, device=a.device, dtype=torch.float32)
     db = torch.empty(C, device=a.device, dtype=torch.float32)
     defer = side is not None
-    L.call("cfm_glu_dwconv_bwd", L.ptr(dy), L.ptr(a), L.dt(a), L.ptr(w_dw), L.ptr(da), L.dt(da),
-           None if defer else L.ptr(dw), None if defer else L.ptr(db), B, T, C, K, L.ptr(ws), L.stream())
-    return _dwconv_wgrad(ws, B, T, C, K, da, dw, db, side)
+    L.call(name, *head, L.ptr(a), L.dt(a), L.ptr(w_dw), L.ptr(da), L.dt(da), None if defer else L.ptr(dw),
+           None if defer else L.ptr(db), B, T, C, K, L.ptr(ws), L.stream())
+    if defer:
+        if getattr(side, "rgroup", None) is not None:
+            np_ = L.load().cfm_convmod_nparts(B, T)
+            dw, db = side.rgroup.add_dwconv(ws, np_, C, K, dw, db)
+        else:
+            side.run(lambda: L.call("cfm_glu_dwconv_bwd_wgrad", L.ptr(ws), B, T, C, K, L.ptr(dw), L.ptr(db),
+                                    L.stream()), ws, dw, db)
+    return da, dw, db
+
+
+def glu_dwconv_bwd(dy, a, w_dw, B, T, C, K, ws, da_dtype, side=None):
+    """side: as _dwconv_bwd."""
+    return _dwconv_bwd("cfm_glu_dwconv_bwd", (L.ptr(dy),), a, w_dw, B, T, C, K, ws, da_dtype, side)
 
 
 def bn_silu_glu_dwconv_bwd(dz, y, gamma, beta, mean, invstd, training, a, w_dw, B, T, C, K, ws, da_dtype,
@@ -818,15 +840,9 @@ def bn_silu_glu_dwconv_bwd(dz, y, gamma, beta, mean, invstd, training, a, w_dw, 
         tot = dbg.clone()
         reduce_sums(tot)
         rows = int(world) * M
-    da = torch.empty(M, 2 * C, device=a.device, dtype=da_dtype)
-    dw = torch.empty(C, K, device=a.device, dtype=torch.float32)
-    db = torch.empty(C, device=a.device, dtype=torch.float32)
-    defer = side is not None
-    L.call("cfm_glu_dwconv_bwd_bn", L.ptr(dz), L.dt(dz), L.ptr(y), L.ptr(gamma), L.ptr(beta), L.ptr(mean),
-           L.ptr(invstd), L.ptr(tot[0]), L.ptr(tot[1]), 1.0 / rows, int(bool(training)), L.ptr(a), L.dt(a),
-           L.ptr(w_dw), L.ptr(da), L.dt(da), None if defer else L.ptr(dw), None if defer else L.ptr(db), B, T, C, K,
-           L.ptr(ws), L.stream())
-    da, dw, db = _dwconv_wgrad(ws, B, T, C, K, da, dw, db, side)
+    head = (L.ptr(dz), L.dt(dz), L.ptr(y), L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(invstd), L.ptr(tot[0]),
+            L.ptr(tot[1]), 1.0 / rows, int(bool(training)))
+    da, dw, db = _dwconv_bwd("cfm_glu_dwconv_bwd_bn", head, a, w_dw, B, T, C, K, ws, da_dtype, side)
     return da, dw, db, dbg[1], dbg[0]
 
 
@@ -857,32 +873,39 @@ def gn_silu_glu_dwconv_bwd(dz, y, gamma, beta, mean, rstd, a, w_dw, B, T, C, K, 
     parameter gradients and the per-sample coefficients (k1, k2) come from cfm_gn_silu_bwd_sums, the GroupNorm
     input gradient is formed inside the depthwise kernel and never stored.  side: as bn_silu_glu_dwconv_bwd.
     Returns (da, dw_dw, db_dw, dgamma, dbeta)."""
-    M = B * T
     dbg = torch.empty(2, C, device=y.device, dtype=torch.float32)     # [dbeta; dgamma]
     coef = torch.empty(B, 2, device=y.device, dtype=torch.float32)    # not in ws: the depthwise kernel overwrites it
     L.call("cfm_gn_silu_bwd_sums", L.ptr(dz), L.dt(dz), L.ptr(y), L.ptr(gamma), L.ptr(beta), L.ptr(mean),
            L.ptr(rstd), B, T, C, L.ptr(ws), L.ptr(dbg[0]), L.ptr(dbg[1]), L.ptr(coef), L.stream())
-    da = torch.empty(M, 2 * C, device=a.device, dtype=da_dtype)
-    dw = torch.empty(C, K, device=a.device, dtype=torch.float32)
-    db = torch.empty(C, device=a.device, dtype=torch.float32)
-    defer = side is not None
-    L.call("cfm_glu_dwconv_bwd_gn", L.ptr(dz), L.dt(dz), L.ptr(y), L.ptr(gamma), L.ptr(beta), L.ptr(mean),
-           L.ptr(rstd), L.ptr(coef), L.ptr(a), L.dt(a), L.ptr(w_dw), L.ptr(da), L.dt(da),
-           None if defer else L.ptr(dw), None if defer else L.ptr(db), B, T, C, K, L.ptr(ws), L.stream())
-    da, dw, db = _dwconv_wgrad(ws, B, T, C, K, da, dw, db, side)
+    head = (L.ptr(dz), L.dt(dz), L.ptr(y), L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(rstd), L.ptr(coef))
+    da, dw, db = _dwconv_bwd("cfm_glu_dwconv_bwd_gn", head, a, w_dw, B, T, C, K, ws, da_dtype, side)
     return da, dw, db, dbg[1], dbg[0]
 
 
-def _dwconv_wgrad(ws, B, T, C, K, da, dw, db, side):
-    defer = side is not None
-    if defer:
-        if getattr(side, "rgroup", None) is not None:
-            np_ = L.load().cfm_convmod_nparts(B, T)
-            dw, db = side.rgroup.add_dwconv(ws, np_, C, K, dw, db)
+def norm_silu_glu_dwconv_bwd(norm, dz, y, gamma, beta, mean, invstd, training, a, w_dw, B, T, C, K, ws, da_dtype,
+                             side=None, reduce_sums=None, world=1, fold=True):
+    """The conv module's backward from dz (the pointwise-conv-2 data gradient) to the GLU input gradient, and the one
+    place that decides how: with the norm backward folded into the depthwise backward where K has such a kernel
+    (dwconv_bwd_folds) and fold is left on, else the norm backward, then the plain depthwise backward of its dy.
+    norm: "bn" (BatchNorm1d; SyncBatchNorm where reduce_sums / world are given and training is on) or "gn"
+    (GroupNorm(1, C): invstd is rstd, training is not read).  fold=False: never fold (CFM_DISABLE=bnfold, A/B).
+    Returns (da, dw_dw, db_dw, dgamma, dbeta, dy): dy is the fp32 norm input gradient, None where it was folded."""
+    gn = norm == "gn"
+    if fold and dwconv_bwd_folds(K):
+        if gn:
+            out = gn_silu_glu_dwconv_bwd(dz, y, gamma, beta, mean, invstd, a, w_dw, B, T, C, K, ws, da_dtype, side=side)
         else:
-            side.run(lambda: L.call("cfm_glu_dwconv_bwd_wgrad", L.ptr(ws), B, T, C, K, L.ptr(dw), L.ptr(db),
-                                    L.stream()), ws, dw, db)
-    return da, dw, db
+            out = bn_silu_glu_dwconv_bwd(dz, y, gamma, beta, mean, invstd, training, a, w_dw, B, T, C, K, ws, da_dtype,
+                                         side=side, reduce_sums=reduce_sums, world=world)
+        return (*out, None)
+    if gn:
+        dy, dgamma, dbeta = gn_silu_bwd(dz, y, gamma, beta, mean, invstd, B, T, ws)
+    elif reduce_sums is not None and training:
+        dy, dgamma, dbeta = bn_silu_bwd_sync(dz, y, gamma, beta, mean, invstd, ws, reduce_sums, world)
+    else:
+        dy, dgamma, dbeta = bn_silu_bwd(dz, y, gamma, beta, mean, invstd, training, ws)
+    da, dw, db = glu_dwconv_bwd(dy, a, w_dw, B, T, C, K, ws, da_dtype, side=side)
+    return da, dw, db, dgamma, dbeta, dy
 
 
 # ----------------------------------------------------------------------------- attention

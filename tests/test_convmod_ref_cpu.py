@@ -13,7 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from nn_conformer_for_speech_recognition_amd import _lib
+from nn_conformer_for_speech_recognition_amd import _lib, ops
 from tests import convmod_ref as R
 
 f64 = torch.float64
@@ -296,3 +296,6 @@ def test_table_reaches_every_family_and_apply_kernel():
     lib = _lib.load()
     assert lib.cfm_convmod_plan(None, None) == -1
     assert set(R.COMPILED_K) == {K for K in range(1, 64, 2) if R.plan(R.OPS["bwd_bn"], _lib.F32, 64, K)[0] == R.KT}
+    # the one fold-or-not predicate the Python callers share says the same
+    for K in range(66):
+        assert ops.dwconv_bwd_folds(K) == (K in R.COMPILED_K), K

@@ -427,6 +427,29 @@ def test_sync_bn_two_shards_in_one_process(T, C, K, dt):
     R.assert_all(checks)
 
 
+@pytest.mark.parametrize("B,T,C,K,dt", [(2, 37, 64, 31, "bf16"), (1, 100, 96, 3, "f32")])
+def test_sync_bn_single_shard_is_the_plain_backward(B, T, C, K, dt):
+    """One shard (M_total = M): cfm_bn_silu_bwd_sums then cfm_bn_silu_bwd_apply is cfm_bn_silu_bwd in training mode bit
+    for bit -- one apply kernel serves both, forming 1 / M from the row count it is handed (the SyncBatchNorm route
+    used to be handed 1 / M_total formed on the host: both are one correctly rounded fp32 division)."""
+    row = next(c for c in R.CASES if (c.T, c.C, c.K, c.dt) == (T, C, K, dt))
+    case = R.Case(B, T, C, K, dt, row.fwd, row.bwd, row.bwd_bn, row.bwd_gn, row.apply, "single shard")
+    M, code = B * T, R.code(dt)
+    d = R.real_inputs(B, T, C, K, torch.Generator().manual_seed(B + T + C + K))
+    ga, gw, gy, ws = forward(case, d["a"], d["w"], d["bias"])
+    gmean, ginv, _, _, _ = bn_forward(case, d, gy, ws, True, case.dtype)
+    gg, gbt, gdz = gin(d["gamma"]), gin(d["beta"]), gin(d["dz"], case.dtype)
+    stat = (P(gy), P(gg), P(gbt), P(gmean), P(ginv))
+    gdy, gdg, gdb = gout(M, C), gout(1, C), gout(1, C)
+    launch("cfm_bn_silu_bwd", P(gdz), code, *stat, 1, P(gdy), P(gdg), P(gdb), M, C, P(ws), outs=(gdy, gdg, gdb, ws))
+    gdbeta, gdgamma, gdy2 = gout(1, C), gout(1, C), gout(M, C)
+    launch("cfm_bn_silu_bwd_sums", P(gdz), code, *stat, M, C, P(ws), P(gdbeta), P(gdgamma), outs=(gdbeta, gdgamma, ws))
+    launch("cfm_bn_silu_bwd_apply", P(gdz), code, *stat, P(gdbeta), P(gdgamma), M, P(gdy2), M, C, outs=(gdy2,))
+    assert torch.equal(host(gdgamma), host(gdg)) and torch.equal(host(gdbeta), host(gdb))
+    assert not torch.isnan(host(gdy)).any()
+    assert torch.equal(host(gdy2), host(gdy)), "the sums + apply pair and cfm_bn_silu_bwd differ"
+
+
 # ------------------------------------------------------------------------------------------ generic BatchNorm
 @pytest.mark.parametrize("M,C", R.BN_SHAPES)
 @pytest.mark.parametrize("act", [0, 1])

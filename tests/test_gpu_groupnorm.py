@@ -92,7 +92,7 @@ def test_gn_convmod_kernels(B, T, C, K, dt):
     yv = ops.glu_dwconv_fwd(ad_, wd_, bd_, B, T, C, K, ws)
     zv, mean, rstd = ops.gn_silu_fwd(yv, gam, bet, 1e-5, B, T, C, ws, dt)
     dzd = dz.to(DEV, dt)
-    fold = K in ops.BN_FOLD_K
+    fold = ops.dwconv_bwd_folds(K)
     if fold:
         da, dw, db, dg, dbt = ops.gn_silu_glu_dwconv_bwd(dzd, yv, gam, bet, mean, rstd, ad_, wd_, B, T, C, K, ws, dt)
     dy, dg2, dbt2 = ops.gn_silu_bwd(dzd, yv, gam, bet, mean, rstd, B, T, ws)
