@@ -566,31 +566,79 @@ enum cfm_attn_mode {
   CFM_ATTN_MODE_DQ_RECOMPUTE = 1 << 10    /* keeps the recomputing whole-head dQ kernel (default: the stored dS) */
 };
 int cfm_attn_set_mode(int mode);
+
+/* What the attention entry points below launch and how the backward workspace is laid out, as a pure host function
+   (csrc/attn_plan.h): cfm_attn_fwd, cfm_attn_bwd_ws_bytes, cfm_attn_bwd and cfm_attn_bwd_ex act on this one rule. */
+enum cfm_attn_path {
+  CFM_ATTN_PATH_SIMT = 0,                 /* fp32, bf16 heads wider than 64, bf16 rel-pos under CFM_ATTN_MODE_REL_SIMT */
+  CFM_ATTN_PATH_HEAD = 1,                 /* bf16 MFMA, one (or qs) workgroups per (b, h): T <= 384 */
+  CFM_ATTN_PATH_TILED = 2,                /* bf16 MFMA, 128 queries per workgroup: T > 384 or CFM_ATTN_MODE_TILED */
+  CFM_ATTN_PATH_REL = 3                   /* bf16 MFMA relative-position kernels */
+};
+enum cfm_attn_dpos {
+  CFM_ATTN_DPOS_NONE = 0,                 /* not the rel-pos MFMA path */
+  CFM_ATTN_DPOS_XCD = 1,                  /* 128 relative rows per workgroup, (b, h) pairs dealt to XCDs (rel_vec only) */
+  CFM_ATTN_DPOS_R4_VEC = 2,               /* round-4 kernel, branch-free loads (CFM_ATTN_MODE_REL_DPOS_R4) */
+  CFM_ATTN_DPOS_R4 = 3                    /* round-4 kernel, zero-filling loads (rel_vec off) */
+};
+enum cfm_attn_ws {                        /* sections of the backward workspace, in address order */
+  CFM_ATTN_WS_D = 0,                      /* D = rowsum(dO * O): B*H*T f32 (MFMA paths) */
+  CFM_ATTN_WS_PART = 1,                   /* rel: du / dv partials, B * 4*ceil(T/128) * 2*H*dk f32 */
+  CFM_ATTN_WS_DS = 2,                     /* head: dS^T, B*H*Tq*Tq bf16 (Tq = ceil(T/32)*32), only when dQ reads it;
+                                             rel: dS, B*H*T*ldS bf16 (ldS = ceil(T/8)*8); SIMT: dS, B*H*T*T f32 */
+  CFM_ATTN_WS_DPOS = 3                    /* rel: per-utterance dpos partials, B*(2T-1)*H*dk f32 */
+};
+typedef struct {
+  int B, T, H, dk, dtype;
+  int rel;                                /* nonzero: relative positions */
+  int qkv_mod16, dout_mod16, pos_mod16;   /* the pointers' addresses modulo 16 (forward: dout_mod16 = qkv_mod16;
+                                             no rel-pos: pos_mod16 = 0) */
+  int mode;                               /* cfm_attn_mode bits */
+  int cus;                                /* compute units of the device */
+  int64_t ws_bytes;                       /* backward workspace offered; < 0: unknown, report the full need */
+} cfm_attn_query;
+typedef struct {
+  int path;                               /* cfm_attn_path */
+  int vec, vec4;                          /* 16-byte / 8-byte loads of qkv and dout rows (vec4: non-rel MFMA only) */
+  int pvec, rel_vec;                      /* rel: 16-byte loads of pos; the branch-free prefetch kernels run */
+  int dbg;                                /* the timing bits of mode the non-rel MFMA kernels read */
+  int qs, waves;                          /* head: workgroups per (b, h), 32-row blocks (waves) per workgroup */
+  int dq_stored;                          /* head, rel: dQ from the dS the dK/dV kernel stores (0: recomputed) */
+  int dpos;                               /* cfm_attn_dpos */
+  size_t lds_head, lds_dkdv, lds_dqs;     /* head: dynamic LDS of the forward / recomputing dQ, dK/dV, dQ-from-dS */
+  size_t ws_off[4], ws_size[4];           /* byte offset and size per cfm_attn_ws section (size 0: absent); every
+                                             offset is a multiple of 256 */
+  size_t ws_total;                        /* end of the last section = cfm_attn_bwd_ws_bytes */
+} cfm_attn_choice;
+/* Calls no GPU API.  CFM_ERR_ARG for a null pointer, cus <= 0 or ws_bytes >= 0 below ws_total of the chosen layout;
+   the shape / dtype errors of cfm_attn_fwd otherwise.  On the whole-head path a ws_bytes that holds D (B*H*T floats)
+   but not dS^T behind it selects the recomputing dQ kernel, as CFM_ATTN_MODE_DQ_RECOMPUTE does. */
+int cfm_attn_plan(const cfm_attn_query* q, cfm_attn_choice* out);
+
 int cfm_attn_fwd(const void* qkv, void* o, float* lse, const int32_t* lengths, const void* pos,
                  const float* pos_u, const float* pos_v, int B, int T, int H, int dk, int dtype,
                  float drop_p, uint64_t seed, void* stream);
+/* The plan's ws_total under the mode in force (0 for a shape the plan rejects). */
 size_t cfm_attn_bwd_ws_bytes(int B, int T, int H, int dk, int rel, int dtype);
+/* ws_bytes: the size of ws.  The launcher lays ws out by the plan for that size under the mode in force at the
+   call, so it never writes past ws_bytes: less than the path's minimum (non-rel MFMA: B*H*T floats; rel-pos: the
+   whole rel layout; SIMT: B*H*T*T floats) is CFM_ERR_ARG and nothing is launched.  On the non-rel whole-head path
+   (T <= 384) a ws that also holds dS^T (cfm_attn_bwd_ws_bytes under mode 0) makes dQ come from the dS^T the dK/dV
+   kernel stores; a smaller one runs the recomputing dQ kernel.  dpos is fp32 and D is computed. */
 int cfm_attn_bwd(const void* qkv, const void* o, const void* dout, const float* lse,
                  const int32_t* lengths, const void* pos, const float* pos_u, const float* pos_v,
                  void* dqkv, float* dpos, float* dpos_u, float* dpos_v, int B, int T, int H,
-                 int dk, int dtype, float drop_p, uint64_t seed, float* ws, void* stream);
-/* The same with D = rowsum(dO * O) already in ws (cfm_gemm_desc.rowdot_* of the GEMM that produced dout):
-   the D kernel is skipped.  bf16 MFMA path only (dk <= 64); rel-pos: ws is the full cfm_attn_bwd_ws_bytes
-   workspace with D in its first B*H*T floats. */
-int cfm_attn_bwd_with_d(const void* qkv, const void* o, const void* dout, const float* lse,
-                        const int32_t* lengths, const void* pos, const float* pos_u, const float* pos_v,
-                        void* dqkv, float* dpos, float* dpos_u, float* dpos_v, int B, int T, int H,
-                        int dk, int dtype, float drop_p, uint64_t seed, float* ws, void* stream);
-/* cfm_attn_bwd (d_ready 0) / cfm_attn_bwd_with_d (d_ready 1) with the projected-table gradient dpos written in
-   dtype_dpos: CFM_F32, or CFM_BF16 on the rel-pos MFMA path (each fp32 column sum rounded as cfm_cast rounds
-   it -- the compute-dtype copy the dW_pos GEMM reads, without an fp32 dpos and a cast pass).  d_ready bit 1 (round 6):
-   ws is the full cfm_attn_bwd_ws_bytes workspace (D, if ready, in its first B*H*T floats) -- the non-rel whole-head
-   path (T <= 384) then computes dQ from the dS^T its dK/dV kernel stores there (cfm_attn_bwd always does). */
+                 int dk, int dtype, float drop_p, uint64_t seed, float* ws, size_t ws_bytes, void* stream);
+/* cfm_attn_bwd with the projected-table gradient dpos written in dtype_dpos: CFM_F32, or CFM_BF16 on the rel-pos
+   MFMA path (each fp32 column sum rounded as cfm_cast rounds it -- the compute-dtype copy the dW_pos GEMM reads,
+   without an fp32 dpos and a cast pass).  d_ready 1: D = rowsum(dO * O) is already in the first B*H*T floats of ws
+   (cfm_gemm_desc.rowdot_* of the GEMM that produced dout) and the D kernel is skipped; bf16 MFMA paths only.
+   d_ready 0: D is computed. */
 int cfm_attn_bwd_ex(const void* qkv, const void* o, const void* dout, const float* lse,
                     const int32_t* lengths, const void* pos, const float* pos_u, const float* pos_v,
                     void* dqkv, void* dpos, int dtype_dpos, float* dpos_u, float* dpos_v, int B, int T,
                     int H, int dk, int dtype, float drop_p, uint64_t seed, int d_ready, float* ws,
-                    void* stream);
+                    size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- ConvSubSampling
  * lib/convsubsampling.py:16-45: Conv2d(1->C1, 7x7, s2) -> Conv2d(C1->C2, 3x3, s2), no padding.

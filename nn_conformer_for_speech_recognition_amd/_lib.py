@@ -99,6 +99,23 @@ ATTN_MODE_REL_ZERO_FILL = 1 << 6
 ATTN_MODE_REL_DPOS_R4 = 1 << 7
 ATTN_MODE_REL_DQ_RECOMPUTE = 1 << 9
 ATTN_MODE_DQ_RECOMPUTE = 1 << 10
+# cfm_attn_path / cfm_attn_dpos / cfm_attn_ws (cfm_attn_plan)
+ATTN_PATH_SIMT, ATTN_PATH_HEAD, ATTN_PATH_TILED, ATTN_PATH_REL = range(4)
+ATTN_DPOS_NONE, ATTN_DPOS_XCD, ATTN_DPOS_R4_VEC, ATTN_DPOS_R4 = range(4)
+ATTN_WS_D, ATTN_WS_PART, ATTN_WS_DS, ATTN_WS_DPOS = range(4)
+
+
+class AttnQuery(ctypes.Structure):
+    """cfm_attn_query (include/cfm.h): one attention call as cfm_attn_plan reads it."""
+    _fields_ = [(n, c_int) for n in ("B", "T", "H", "dk", "dtype", "rel", "qkv_mod16", "dout_mod16", "pos_mod16",
+                                     "mode", "cus")] + [("ws_bytes", ctypes.c_int64)]
+
+
+class AttnChoice(ctypes.Structure):
+    """cfm_attn_choice (include/cfm.h)."""
+    _fields_ = [(n, c_int) for n in ("path", "vec", "vec4", "pvec", "rel_vec", "dbg", "qs", "waves", "dq_stored",
+                                     "dpos")] + [(n, c_size_t) for n in ("lds_head", "lds_dkdv", "lds_dqs")] + [
+        ("ws_off", c_size_t * 4), ("ws_size", c_size_t * 4), ("ws_total", c_size_t)]
 
 
 class ConvmodQuery(ctypes.Structure):
@@ -179,6 +196,7 @@ _SIGS = {
                                          c_int, c_int, c_long]),
     "cfm_colreduce_group": (c_int, [c_void_p, c_int, c_long, c_void_p]),
     "cfm_attn_set_mode": (c_int, [c_int]),
+    "cfm_attn_plan": (c_int, [c_void_p, c_void_p]),
     "cfm_colreduce": (c_int, [c_void_p, c_int, c_long, c_long, c_void_p, c_int, c_void_p]),
     "cfm_colsum": (c_int, [c_void_p, c_int, c_long, c_int, c_long, c_void_p, c_int, c_void_p, c_void_p]),
     "cfm_layernorm_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
@@ -249,13 +267,10 @@ _SIGS = {
     "cfm_attn_bwd_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "cfm_attn_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
-                             c_u64, c_void_p, c_void_p]),
-    "cfm_attn_bwd_with_d": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                             c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
-                             c_u64, c_void_p, c_void_p]),
+                             c_u64, c_void_p, c_size_t, c_void_p]),
     "cfm_attn_bwd_ex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                c_float, c_u64, c_int, c_void_p, c_void_p]),
+                                c_float, c_u64, c_int, c_void_p, c_size_t, c_void_p]),
     "cfm_conv1_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "cfm_conv2_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                               c_int, c_void_p]),

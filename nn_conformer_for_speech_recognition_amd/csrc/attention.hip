@@ -16,24 +16,6 @@
 // loops over key tiles: S^T, dP^T, dQ^T += K^T dS^T), plus a tiny D = rowsum(dO*O) kernel.
 // Head dims below 64 (Conformer-S: 36) are zero-padded to 64 in LDS/registers.
 // lse is saved in natural-log units of the scaled scores (same convention as attention_simt).
-#include "cfm_common.h"
-
-namespace cfm {
-int attn_simt_fwd_launch(const void*, void*, float*, const int32_t*, const void*, const float*, const float*, int,
-                         int, int, int, int, float, uint64_t, hipStream_t);
-size_t attn_simt_ws_bytes(int B, int T, int H);
-size_t attn_rel_ws_bytes(int B, int T, int H, int dk);
-extern int g_rel_mode;   // attention_rel.hip: cfm_attn_set_mode's bits for the rel-pos kernels
-int attn_rel_fwd_launch(const void* qkv, void* o, float* lse, const int32_t* len, const void* pos, const float* pu,
-                        const float* pv, int B, int T, int H, int dk, float drop_p, uint64_t seed, hipStream_t s);
-int attn_rel_bwd_launch(const void* qkv, const void* dout, const float* lse, const int32_t* len, const void* pos,
-                        const float* pu, const float* pv, void* dqkv, void* dpos, int dpos_dt, float* dpu, float* dpv,
-                        int B, int T, int H, int dk, float drop_p, uint64_t seed, float* ws, hipStream_t s);
-int attn_simt_bwd_launch(const void*, const void*, const void*, const float*, const int32_t*, const void*,
-                         const float*, const float*, void*, float*, float*, float*, int, int, int, int, int, float,
-                         uint64_t, float*, hipStream_t);
-}  // namespace cfm
-
 #include "attn_common.h"
 
 namespace {
@@ -143,7 +125,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnM p, bf16* __restrict
 // loads, eight in flight per thread), then every wave runs its 32-query block over the staged keys
 // with no further barriers.  B*H workgroups (256 at Conformer-L B=32: one per CU) instead of
 // ceil(T/128)*B*H workgroups that each re-stream K/V tile by tile behind a barrier per tile.
-constexpr int HEAD_TMAX = 384;      // 12 waves of 32 queries; K+V images 2 * 384 * 144 B = 108 KiB
+// (HEAD_TMAX = 384, attn_plan.h: 12 waves of 32 queries; K+V images 2 * 384 * 144 B = 108 KiB)
 
 // the whole-head kernels' work split: when B*H workgroups would leave CUs idle (Conformer-S / M: 4 heads, B*H = 128
 // on 256 CUs) each (b, h) runs as p.qs workgroups, each staging the whole head and sweeping its own contiguous range
@@ -204,7 +186,7 @@ __device__ __forceinline__ void head_stage(const AttnM& p, const bf16* base0, co
   }
 }
 
-// forward: grid (B*H), block 64 * ceil(T/32); dynamic LDS head_lds_bytes(T)
+// forward: grid (B*H*qs), block 64 * waves; dynamic LDS: the plan's lds_head
 __global__ __launch_bounds__(64 * HEAD_TMAX / 32) void attn_fwd_head_kernel(AttnM p, bf16* __restrict__ o,
                                                                             float* __restrict__ lse) {
   if (p.drop_p > 0.f) p.seed = salted_seed(p.seed, p.salt);
@@ -577,12 +559,6 @@ __global__ __launch_bounds__(64 * HEAD_TMAX / 32) void attn_bwd_dkdv_wave_kernel
 // a private 4 KiB LDS image (64-B rows, conflict free for the same reads; the next slice in registers while the
 // current one runs) -- no workgroup barrier inside the loop.  Keys >= len read as zero.  After the loop the LDS holds
 // the waves' f32 stages of the dq store.
-constexpr int DQH_KS = 96;
-size_t dqs_head_lds_bytes(int T, int waves) {
-  const size_t tk = (size_t)cdiv(T, TILE) * TILE;   // K rows: whole 64-key tiles (rows >= T zero)
-  const size_t loop = tk * DQH_KS * 2 + (size_t)waves * TILE * 32 * 2, stage = (size_t)waves * 32 * 65 * 4;
-  return loop > stage ? loop : stage;
-}
 __global__ __launch_bounds__(64 * HEAD_TMAX / 32) void attn_bwd_dqs_head_kernel(AttnM p, const bf16* __restrict__ dsT,
                                                                                 bf16* __restrict__ dqkv) {
   extern __shared__ __attribute__((aligned(16))) bf16 hsm[];
@@ -646,11 +622,6 @@ __global__ __launch_bounds__(64 * HEAD_TMAX / 32) void attn_bwd_dqs_head_kernel(
   if (q0 < p.T)
     store_transposed(st, a0, a1, p.scale, dqkv + (long)b * p.T * p.D3 + h * p.dk, p.D3, q0, min(32, p.T - q0), p.dk,
                      lane);
-}
-
-size_t dkdv_wave_lds_bytes(int T, int waves) {
-  const size_t nq = (size_t)cdiv(T, 32), rows = nq * 32;
-  return 2 * rows * KS * sizeof(bf16) + 2 * rows * sizeof(float) + (size_t)waves * nq * 64 * sizeof(unsigned short);
 }
 
 // ------------------------------------------------------------------------------------ D = rowsum(dO*O)
@@ -871,156 +842,105 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_kernel(AttnM p, const bf16*
   store_transposed(stage, dv0, dv1, 1.f, base + 2 * p.HD, p.D3, k0w, nvalid, p.dk, lane);
 }
 
-// bf16 runs on MFMA (pos != nullptr: attention_rel.hip); fp32 (the parity mode) on the SIMT kernels.
-// CFM_ATTN_MODE_REL_SIMT sends bf16 rel-pos back to SIMT (A/B, parity cross-check).
-int g_attn_mode = 0;
-bool use_mfma(int dtype, const void* pos, int dk) {
-  return dtype == CFM_BF16 && dk <= DKP && (pos == nullptr || (g_attn_mode & CFM_ATTN_MODE_REL_SIMT) == 0);
-}
 
-// whole-head kernels: T <= HEAD_TMAX; CFM_ATTN_MODE_TILED forces the tiled kernels (A/B, parity)
-bool use_head(int T) { return T <= HEAD_TMAX && (g_attn_mode & CFM_ATTN_MODE_TILED) == 0; }
-size_t head_lds_bytes(int T, int waves) {
-  const size_t rows = (size_t)cdiv(T, TILE) * TILE;
-  const size_t img = 2 * rows * KS * sizeof(bf16);
-  const size_t stage = (size_t)waves * 32 * 65 * sizeof(float);
-  return img > stage ? img : stage;
-}
-
-
-// workgroups per (b, h) of the whole-head kernels: enough to give every CU one (B*H*qs <= CUs), at most 4 and at most
-// one 32-row block each (CFM_ATTN_MODE_REL_ZERO_FILL: always one, A/B)
-int head_split(int B, int H, int T) {
-  if (g_attn_mode & CFM_ATTN_MODE_REL_ZERO_FILL) return 1;
-  const int nb = cdiv(T, 32), bh = B * H, cus = cfm::num_cus();
-  int qs = 1;
-  while (qs < 4 && qs < nb && (long)bh * (qs + 1) <= cus) ++qs;
-  return qs;
+// what an entry point knows of a call, as the plan reads it (mode and CU count of the moment of the call)
+cfm_attn_query attn_query(const void* qkv, const void* dout, const void* pos, int B, int T, int H, int dk, int dtype,
+                          int64_t ws_bytes) {
+  return cfm_attn_query{B, T, H, dk, dtype, pos != nullptr, (int)((uintptr_t)qkv % 16), (int)((uintptr_t)dout % 16),
+                        (int)((uintptr_t)pos % 16), cfm::g_attn_mode, cfm::num_cus(), ws_bytes};
 }
 
 }  // namespace
+
+namespace cfm {
+int g_attn_mode = 0;
+}
+
+CFM_EXPORT int cfm_attn_set_mode(int mode) {
+  cfm::g_attn_mode = mode;
+  return CFM_OK;
+}
+
+CFM_EXPORT int cfm_attn_plan(const cfm_attn_query* q, cfm_attn_choice* out) {
+  CFM_REQUIRE(q && out, CFM_ERR_ARG, "null pointer");
+  return attn_plan(*q, *out, __func__);
+}
 
 CFM_EXPORT int cfm_attn_fwd(const void* qkv, void* o, float* lse, const int32_t* lengths, const void* pos,
                             const float* pos_u, const float* pos_v, int B, int T, int H, int dk, int dtype,
                             float drop_p, uint64_t seed, void* stream) {
   CFM_REQUIRE(qkv && o && lse && lengths, CFM_ERR_ARG, "null pointer");
-  CFM_REQUIRE(B > 0 && T > 0 && H > 0 && dk > 0 && dk <= 1024, CFM_ERR_SHAPE, "bad shape");
   CFM_REQUIRE(!pos || (pos_u && pos_v), CFM_ERR_ARG, "rel-pos needs pos_u and pos_v");
-  CFM_REQUIRE(dtype == CFM_BF16 || dtype == CFM_F32, CFM_ERR_DTYPE, "dtype");
-  CFM_REQUIRE(pos || dtype == CFM_F32 || dk <= DKP, CFM_ERR_UNSUPPORTED, "bf16 head dim must be <= 64");
-  CFM_REQUIRE((double)B * H * T * (T + 1) < 8589934592.0, CFM_ERR_SHAPE, "attention dropout index space (2^33)");
+  cfm_attn_choice c;
+  if (const int rc = attn_plan(attn_query(qkv, qkv, pos, B, T, H, dk, dtype, -1), c, __func__)) return rc;
   hipStream_t s = cfm::as_stream(stream);
-  if (!use_mfma(dtype, pos, dk))
+  if (c.path == CFM_ATTN_PATH_SIMT)
     return cfm::attn_simt_fwd_launch(qkv, o, lse, lengths, pos, pos_u, pos_v, B, T, H, dk, dtype, drop_p, seed, s);
-  if (pos)
-    return cfm::attn_rel_fwd_launch(qkv, o, lse, lengths, pos, pos_u, pos_v, B, T, H, dk, drop_p, seed, s);
-  AttnM p{(const bf16*)qkv, B, T, H, dk, 3 * H * dk, H * dk, lengths, 1.f / sqrtf((float)dk), drop_p, seed,
-          ((uintptr_t)qkv % 16 == 0) && (dk % 8 == 0) && ((3 * H * dk) % 8 == 0), g_attn_mode & (CFM_ATTN_MODE_STAGING_ONLY | CFM_ATTN_MODE_SKIP_STORES),
-          cfm::g_rng_salt};
-  p.vec4 = ((uintptr_t)qkv % 8 == 0) && (dk % 4 == 0) && ((3 * H * dk) % 4 == 0);
-  if (use_head(T)) {
-    // LDS sized for the full padded length (lengths are device data; len <= T)
-    p.qs = head_split(B, H, T);
-    const int waves = cdiv(cdiv(T, 32), p.qs);
-    hipLaunchKernelGGL(attn_fwd_head_kernel, dim3(B * H * p.qs), dim3(64 * waves), head_lds_bytes(T, waves), s, p,
-                       (bf16*)o, lse);
-    return cfm::check_launch("cfm_attn_fwd");
-  }
-  hipLaunchKernelGGL(attn_fwd_kernel, dim3(cdiv(T, 128), H, B), dim3(256), 0, s, p, (bf16*)o, lse);
+  if (c.path == CFM_ATTN_PATH_REL)
+    return cfm::attn_rel_fwd_launch(c, qkv, o, lse, lengths, pos, pos_u, pos_v, B, T, H, dk, drop_p, seed, s);
+  const AttnM p = make_attnm(c, qkv, lengths, B, T, H, dk, drop_p, seed);
+  if (c.path == CFM_ATTN_PATH_HEAD)
+    hipLaunchKernelGGL(attn_fwd_head_kernel, dim3(B * H * c.qs), dim3(64 * c.waves), c.lds_head, s, p, (bf16*)o, lse);
+  else
+    hipLaunchKernelGGL(attn_fwd_kernel, dim3(cdiv(T, 128), H, B), dim3(256), 0, s, p, (bf16*)o, lse);
   return cfm::check_launch("cfm_attn_fwd");
 }
 
-// the whole-head backward's dS^T buffer (dQ from dS): after D in the full workspace
-static bool dsT_path(int T) { return use_head(T) && !(g_attn_mode & CFM_ATTN_MODE_DQ_RECOMPUTE); }
-static size_t d_slot_bytes(int B, int T, int H) { return ((size_t)B * H * T * sizeof(float) + 255) & ~(size_t)255; }
-static size_t dsT_bytes(int B, int T, int H) { const size_t tq = (size_t)cdiv(T, 32) * 32; return (size_t)B * H * tq * tq * 2; }
-
 CFM_EXPORT size_t cfm_attn_bwd_ws_bytes(int B, int T, int H, int dk, int rel, int dtype) {
-  if (!use_mfma(dtype, rel ? (const void*)1 : nullptr, dk)) return cfm::attn_simt_ws_bytes(B, T, H);
-  if (rel) return cfm::attn_rel_ws_bytes(B, T, H, dk);
-  if (dsT_path(T)) return d_slot_bytes(B, T, H) + dsT_bytes(B, T, H);
-  return (size_t)B * H * T * sizeof(float);
+  // the CU count moves no section: 1, so that sizing a workspace does not ask the device
+  const cfm_attn_query q{B, T, H, dk, dtype, rel, 0, 0, 0, cfm::g_attn_mode, 1, -1};
+  cfm_attn_choice c;
+  return attn_plan(q, c, __func__) == CFM_OK ? c.ws_total : 0;
 }
 
-static int attn_bwd_impl(const void* qkv, const void* o, const void* dout, const float* lse,
-                         const int32_t* lengths, const void* pos, const float* pos_u, const float* pos_v,
-                         void* dqkv, void* dpos, int dpos_dt, float* dpos_u, float* dpos_v, int B, int T, int H,
-                         int dk, int dtype, float drop_p, uint64_t seed, float* ws, void* stream, bool d_ready,
-                         bool full_ws) {
+CFM_EXPORT int cfm_attn_bwd_ex(const void* qkv, const void* o, const void* dout, const float* lse,
+                               const int32_t* lengths, const void* pos, const float* pos_u, const float* pos_v,
+                               void* dqkv, void* dpos, int dpos_dt, float* dpos_u, float* dpos_v, int B, int T,
+                               int H, int dk, int dtype, float drop_p, uint64_t seed, int d_ready, float* ws,
+                               size_t ws_bytes, void* stream) {
   CFM_REQUIRE(qkv && o && dout && lse && lengths && dqkv && ws, CFM_ERR_ARG, "null pointer");
-  CFM_REQUIRE(B > 0 && T > 0 && H > 0 && dk > 0, CFM_ERR_SHAPE, "bad shape");
   CFM_REQUIRE(!pos || (pos_u && pos_v && dpos && dpos_u && dpos_v), CFM_ERR_ARG, "rel-pos grads need buffers");
-  hipStream_t s = cfm::as_stream(stream);
-  CFM_REQUIRE(!d_ready || use_mfma(dtype, pos, dk), CFM_ERR_UNSUPPORTED, "precomputed D: bf16 MFMA path only");
-  CFM_REQUIRE(dpos_dt == CFM_F32 || (dpos_dt == CFM_BF16 && pos && use_mfma(dtype, pos, dk)), CFM_ERR_DTYPE,
+  CFM_REQUIRE(ws_bytes <= (size_t)INT64_MAX, CFM_ERR_ARG, "ws_bytes");
+  cfm_attn_choice c;
+  if (const int rc = attn_plan(attn_query(qkv, dout, pos, B, T, H, dk, dtype, (int64_t)ws_bytes), c, __func__)) return rc;
+  const bool mfma = c.path != CFM_ATTN_PATH_SIMT;
+  CFM_REQUIRE(!d_ready || mfma, CFM_ERR_UNSUPPORTED, "precomputed D: bf16 MFMA path only");
+  CFM_REQUIRE(dpos_dt == CFM_F32 || (dpos_dt == CFM_BF16 && pos && mfma), CFM_ERR_DTYPE,
               "dpos: fp32, or bf16 on the rel-pos MFMA path");
-  if (!use_mfma(dtype, pos, dk))
+  hipStream_t s = cfm::as_stream(stream);
+  if (!mfma)
     return cfm::attn_simt_bwd_launch(qkv, o, dout, lse, lengths, pos, pos_u, pos_v, dqkv, (float*)dpos, dpos_u,
-                                     dpos_v, B, T, H, dk, dtype, drop_p, seed, ws, s);
-  AttnM p{(const bf16*)qkv, B, T, H, dk, 3 * H * dk, H * dk, lengths, 1.f / sqrtf((float)dk), drop_p, seed,
-          ((uintptr_t)qkv % 16 == 0) && ((uintptr_t)dout % 16 == 0) && (dk % 8 == 0) && ((3 * H * dk) % 8 == 0),
-          g_attn_mode & (CFM_ATTN_MODE_STAGING_ONLY | CFM_ATTN_MODE_SKIP_STORES), cfm::g_rng_salt};
-  p.vec4 = ((uintptr_t)qkv % 8 == 0) && ((uintptr_t)dout % 8 == 0) && (dk % 4 == 0) && ((3 * H * dk) % 4 == 0);
-  const long nrow = (long)B * H * T;
-  (void)nrow;
+                                     dpos_v, B, T, H, dk, dtype, drop_p, seed, attn_ws_ptr<float>(c, CFM_ATTN_WS_DS, ws), s);
   CFM_REQUIRE(H * dk <= 1024, CFM_ERR_UNSUPPORTED, "H*dk must be <= 1024");
+  float* D = attn_ws_ptr<float>(c, CFM_ATTN_WS_D, ws);
   if (!d_ready)
     hipLaunchKernelGGL(attn_bwd_dot_kernel, dim3((unsigned)(((long)B * T + 3) / 4)), dim3(256), 0, s,
-                       (const bf16*)dout, (const bf16*)o, ws, B, T, H, dk);
-  if (pos)
-    return cfm::attn_rel_bwd_launch(qkv, dout, lse, lengths, pos, pos_u, pos_v, dqkv, dpos, dpos_dt, dpos_u, dpos_v, B,
-                                    T, H, dk, drop_p, seed, ws, s);
-  p.qs = use_head(T) ? head_split(B, H, T) : 1;
-  const int hwaves = cdiv(cdiv(T, 32), p.qs);
-  // dQ from the dS^T the dK/dV kernel stores: only when the caller passed the full workspace (cfm_attn_bwd, or
-  // cfm_attn_bwd_ex with d_ready bit 1; cfm_attn_bwd_with_d's ws may be D alone)
-  bf16* dsT = full_ws && dsT_path(T) ? reinterpret_cast<bf16*>(reinterpret_cast<char*>(ws) + d_slot_bytes(B, T, H))
-                                     : nullptr;
-  if (use_head(T))
-    hipLaunchKernelGGL(attn_bwd_dkdv_wave_kernel, dim3(B * H * p.qs), dim3(64 * hwaves), dkdv_wave_lds_bytes(T, hwaves),
-                       s, p, (const bf16*)dout, lse, ws, (bf16*)dqkv, dsT);
-  else
-    hipLaunchKernelGGL(attn_bwd_dkdv_kernel, dim3(cdiv(T, 128), H, B), dim3(256), 0, s, p, (const bf16*)dout, lse,
-                       ws, (bf16*)dqkv);
+                       (const bf16*)dout, (const bf16*)o, D, B, T, H, dk);
+  if (c.path == CFM_ATTN_PATH_REL)
+    return cfm::attn_rel_bwd_launch(c, qkv, dout, lse, lengths, pos, pos_u, pos_v, dqkv, dpos, dpos_dt, dpos_u, dpos_v,
+                                    B, T, H, dk, drop_p, seed, ws, s);
+  const AttnM p = make_attnm(c, qkv, lengths, B, T, H, dk, drop_p, seed);
+  if (c.path == CFM_ATTN_PATH_TILED) {
+    const dim3 grid(cdiv(T, 128), H, B);
+    hipLaunchKernelGGL(attn_bwd_dkdv_kernel, grid, dim3(256), 0, s, p, (const bf16*)dout, lse, D, (bf16*)dqkv);
+    hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, dim3(256), 0, s, p, (const bf16*)dout, lse, D, (bf16*)dqkv);
+    return cfm::check_launch("cfm_attn_bwd");
+  }
+  // whole-head: dK/dV (which stores dS^T where the plan gave it a section), then dQ from it or recomputed
+  const dim3 grid(B * H * c.qs), block(64 * c.waves);
+  bf16* dsT = c.dq_stored ? attn_ws_ptr<bf16>(c, CFM_ATTN_WS_DS, ws) : nullptr;
+  hipLaunchKernelGGL(attn_bwd_dkdv_wave_kernel, grid, block, c.lds_dkdv, s, p, (const bf16*)dout, lse, D, (bf16*)dqkv, dsT);
   if (dsT)
-    hipLaunchKernelGGL(attn_bwd_dqs_head_kernel, dim3(B * H * p.qs), dim3(64 * hwaves), dqs_head_lds_bytes(T, hwaves), s,
-                       p, (const bf16*)dsT, (bf16*)dqkv);
-  else if (use_head(T))
-    hipLaunchKernelGGL(attn_bwd_dq_head_kernel, dim3(B * H * p.qs), dim3(64 * hwaves), head_lds_bytes(T, hwaves), s, p,
-                       (const bf16*)dout, lse, ws, (bf16*)dqkv);
+    hipLaunchKernelGGL(attn_bwd_dqs_head_kernel, grid, block, c.lds_dqs, s, p, (const bf16*)dsT, (bf16*)dqkv);
   else
-    hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(cdiv(T, 128), H, B), dim3(256), 0, s, p, (const bf16*)dout, lse, ws,
-                       (bf16*)dqkv);
+    hipLaunchKernelGGL(attn_bwd_dq_head_kernel, grid, block, c.lds_head, s, p, (const bf16*)dout, lse, D, (bf16*)dqkv);
   return cfm::check_launch("cfm_attn_bwd");
 }
 
 CFM_EXPORT int cfm_attn_bwd(const void* qkv, const void* o, const void* dout, const float* lse,
                             const int32_t* lengths, const void* pos, const float* pos_u, const float* pos_v,
                             void* dqkv, float* dpos, float* dpos_u, float* dpos_v, int B, int T, int H, int dk,
-                            int dtype, float drop_p, uint64_t seed, float* ws, void* stream) {
-  return attn_bwd_impl(qkv, o, dout, lse, lengths, pos, pos_u, pos_v, dqkv, dpos, CFM_F32, dpos_u, dpos_v, B, T, H, dk,
-                       dtype, drop_p, seed, ws, stream, false, true);
-}
-
-CFM_EXPORT int cfm_attn_bwd_with_d(const void* qkv, const void* o, const void* dout, const float* lse,
-                                   const int32_t* lengths, const void* pos, const float* pos_u, const float* pos_v,
-                                   void* dqkv, float* dpos, float* dpos_u, float* dpos_v, int B, int T, int H, int dk,
-                                   int dtype, float drop_p, uint64_t seed, float* ws, void* stream) {
-  return attn_bwd_impl(qkv, o, dout, lse, lengths, pos, pos_u, pos_v, dqkv, dpos, CFM_F32, dpos_u, dpos_v, B, T, H, dk,
-                       dtype, drop_p, seed, ws, stream, true, false);
-}
-
-CFM_EXPORT int cfm_attn_bwd_ex(const void* qkv, const void* o, const void* dout, const float* lse,
-                               const int32_t* lengths, const void* pos, const float* pos_u, const float* pos_v,
-                               void* dqkv, void* dpos, int dtype_dpos, float* dpos_u, float* dpos_v, int B, int T,
-                               int H, int dk, int dtype, float drop_p, uint64_t seed, int d_ready, float* ws,
-                               void* stream) {
-  return attn_bwd_impl(qkv, o, dout, lse, lengths, pos, pos_u, pos_v, dqkv, dpos, dtype_dpos, dpos_u, dpos_v, B, T, H,
-                       dk, dtype, drop_p, seed, ws, stream, (d_ready & 1) != 0, (d_ready & 2) != 0);
-}
-
-CFM_EXPORT int cfm_attn_set_mode(int mode) {
-  g_attn_mode = mode;
-  cfm::g_rel_mode = mode;
-  return CFM_OK;
+                            int dtype, float drop_p, uint64_t seed, float* ws, size_t ws_bytes, void* stream) {
+  return cfm_attn_bwd_ex(qkv, o, dout, lse, lengths, pos, pos_u, pos_v, dqkv, dpos, CFM_F32, dpos_u, dpos_v, B, T, H, dk,
+                         dtype, drop_p, seed, 0, ws, ws_bytes, stream);
 }

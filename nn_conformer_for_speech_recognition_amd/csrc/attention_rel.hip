@@ -1278,98 +1278,65 @@ __global__ __launch_bounds__(256) void attn_rel_bwd_dpos3_kernel(AttnM p, RelP r
 
 namespace cfm {
 
-// workspace of the rel-pos MFMA backward: [D (B*H*T f32)] [du/dv partials] [dS (B*H*T*ldS bf16)]
-// [per-utterance dpos partials (B*(2T-1)*H*dk f32)]
-static inline int rel_ldS(int T) { return (T + 7) & ~7; }
-static inline size_t rel_part_floats(int B, int T, int H, int dk) { return (size_t)B * 4 * cdiv(T, 128) * 2 * H * dk; }
-
-size_t attn_rel_ws_bytes(int B, int T, int H, int dk) {
-  const size_t d = (size_t)B * H * T * sizeof(float);
-  const size_t part = rel_part_floats(B, T, H, dk) * sizeof(float);
-  const size_t ds = (size_t)B * H * T * rel_ldS(T) * sizeof(bf16);
-  const size_t dpos_part = (size_t)B * (2 * T - 1) * H * dk * sizeof(float);
-  return ((d + 255) & ~(size_t)255) + ((part + 255) & ~(size_t)255) + ((ds + 255) & ~(size_t)255) + dpos_part;
+static RelP make_relp(const cfm_attn_choice& c, const void* pos, const float* pu, const float* pv) {
+  return RelP{(const bf16*)pos, pu, pv, c.pvec != 0};
 }
 
-static RelP make_relp(const void* pos, const float* pu, const float* pv, int dk) {
-  return RelP{(const bf16*)pos, pu, pv, ((uintptr_t)pos % 16 == 0) && (dk % 8 == 0)};
+// The one VEC switch: f(std::true_type{}) for the branch-free prefetch kernels (the plan's rel_vec: dk = 64 with
+// 16-B aligned rows of qkv / dout / pos), f(std::false_type{}) for the zero-filling ones.
+template <typename F>
+static void with_vec(bool vec, F&& f) {
+  if (vec) f(std::true_type{});
+  else f(std::false_type{});
 }
 
-// branch-free prefetch kernels (ld8c): dk = 64 with 16-B aligned rows of qkv / dout / pos.
-// CFM_ATTN_MODE_REL_ZERO_FILL keeps the zero-filling loads (A/B)
-int g_rel_mode = 0;
-static bool rel_vec(const AttnM& p, const RelP& rp) {
-  return p.vec && rp.pvec && p.dk == 64 && !(g_rel_mode & CFM_ATTN_MODE_REL_ZERO_FILL);
-}
-
-static AttnM make_attnm(const void* qkv, const void* dout, const int32_t* len, int B, int T, int H, int dk,
-                        float drop_p, uint64_t seed) {
-  AttnM p{(const bf16*)qkv, B, T, H, dk, 3 * H * dk, H * dk, len, 1.f / sqrtf((float)dk), drop_p, seed,
-          ((uintptr_t)qkv % 16 == 0) && ((uintptr_t)dout % 16 == 0) && (dk % 8 == 0) && ((3 * H * dk) % 8 == 0), 0,
-          g_rng_salt};
-  return p;
-}
-
-int attn_rel_fwd_launch(const void* qkv, void* o, float* lse, const int32_t* len, const void* pos, const float* pu,
-                        const float* pv, int B, int T, int H, int dk, float drop_p, uint64_t seed, hipStream_t s) {
-  const AttnM p = make_attnm(qkv, qkv, len, B, T, H, dk, drop_p, seed);
-  const RelP rp = make_relp(pos, pu, pv, p.dk);
-  const dim3 grid(cdiv(p.T, 128), p.H, p.B);
-  if (rel_vec(p, rp)) hipLaunchKernelGGL(attn_rel_fwd2_kernel<true>, grid, dim3(256), 0, s, p, rp, (bf16*)o, lse);
-  else hipLaunchKernelGGL(attn_rel_fwd2_kernel<false>, grid, dim3(256), 0, s, p, rp, (bf16*)o, lse);
+int attn_rel_fwd_launch(const cfm_attn_choice& c, const void* qkv, void* o, float* lse, const int32_t* len,
+                        const void* pos, const float* pu, const float* pv, int B, int T, int H, int dk, float drop_p,
+                        uint64_t seed, hipStream_t s) {
+  const AttnM p = make_attnm(c, qkv, len, B, T, H, dk, drop_p, seed);
+  const RelP rp = make_relp(c, pos, pu, pv);
+  with_vec(c.rel_vec, [&](auto v) {
+    hipLaunchKernelGGL(attn_rel_fwd2_kernel<decltype(v)::value>, dim3(cdiv(T, 128), H, B), dim3(256), 0, s, p, rp,
+                       (bf16*)o, lse);
+  });
   return check_launch("cfm_attn_fwd(rel)");
 }
 
-// D (rowsum dO*O per head) must already be in ws[0 .. B*H*T)
-int attn_rel_bwd_launch(const void* qkv, const void* dout, const float* lse, const int32_t* len, const void* pos,
-                        const float* pu, const float* pv, void* dqkv, void* dpos, int dpos_dt, float* dpu, float* dpv,
-                        int B, int T, int H, int dk, float drop_p, uint64_t seed, float* ws, hipStream_t s) {
-  AttnM p = make_attnm(qkv, dout, len, B, T, H, dk, drop_p, seed);
-  const RelP rp = make_relp(pos, pu, pv, p.dk);
-  const size_t d_bytes = ((size_t)p.B * p.H * p.T * sizeof(float) + 255) & ~(size_t)255;
-  float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + d_bytes);
-  const size_t part_bytes = (rel_part_floats(p.B, p.T, p.H, p.dk) * sizeof(float) + 255) & ~(size_t)255;
-  bf16* dsbuf = reinterpret_cast<bf16*>(reinterpret_cast<char*>(part) + part_bytes);
-  const int ldS = rel_ldS(p.T);
-  const dim3 grid(cdiv(p.T, 128), p.H, p.B);
-  // dK / dV (+ the dS buffer), then dQ: from the stored dS (default) or recomputed (CFM_ATTN_MODE_REL_DQ_RECOMPUTE)
-  const bool dq_recompute = (g_rel_mode & CFM_ATTN_MODE_REL_DQ_RECOMPUTE) != 0;
-  if (rel_vec(p, rp)) {
-    hipLaunchKernelGGL(attn_rel_bwd_dkdv_kernel<true>, grid, dim3(256), 0, s, p, rp, (const bf16*)dout, lse, ws,
+int attn_rel_bwd_launch(const cfm_attn_choice& c, const void* qkv, const void* dout, const float* lse,
+                        const int32_t* len, const void* pos, const float* pu, const float* pv, void* dqkv, void* dpos,
+                        int dpos_dt, float* dpu, float* dpv, int B, int T, int H, int dk, float drop_p, uint64_t seed,
+                        float* ws, hipStream_t s) {
+  const AttnM p = make_attnm(c, qkv, len, B, T, H, dk, drop_p, seed);
+  const RelP rp = make_relp(c, pos, pu, pv);
+  float* part = attn_ws_ptr<float>(c, CFM_ATTN_WS_PART, ws);
+  bf16* dsbuf = attn_ws_ptr<bf16>(c, CFM_ATTN_WS_DS, ws);
+  float* dpos_part = attn_ws_ptr<float>(c, CFM_ATTN_WS_DPOS, ws);
+  const int ldS = (T + 7) & ~7, nrel = 2 * T - 1;
+  const dim3 grid(cdiv(T, 128), H, B);
+  // dK / dV (+ the dS buffer), then dQ from the stored dS or recomputed, then dpos
+  with_vec(c.rel_vec, [&](auto v) {
+    constexpr bool VEC = decltype(v)::value;
+    hipLaunchKernelGGL(attn_rel_bwd_dkdv_kernel<VEC>, grid, dim3(256), 0, s, p, rp, (const bf16*)dout, lse, ws,
                        (bf16*)dqkv, dsbuf, ldS);
-    if (dq_recompute)
-      hipLaunchKernelGGL(attn_rel_bwd_dq2_kernel<true>, grid, dim3(256), 0, s, p, rp, (const bf16*)dout, lse, ws,
+    if (c.dq_stored)
+      hipLaunchKernelGGL(attn_rel_bwd_dqs_kernel<VEC>, grid, dim3(256), 0, s, p, rp, (const bf16*)dsbuf, ldS,
                          (bf16*)dqkv, part);
     else
-      hipLaunchKernelGGL(attn_rel_bwd_dqs_kernel<true>, grid, dim3(256), 0, s, p, rp, (const bf16*)dsbuf, ldS,
+      hipLaunchKernelGGL(attn_rel_bwd_dq2_kernel<VEC>, grid, dim3(256), 0, s, p, rp, (const bf16*)dout, lse, ws,
                          (bf16*)dqkv, part);
-  } else {
-    hipLaunchKernelGGL(attn_rel_bwd_dkdv_kernel<false>, grid, dim3(256), 0, s, p, rp, (const bf16*)dout, lse, ws,
-                       (bf16*)dqkv, dsbuf, ldS);
-    if (dq_recompute)
-      hipLaunchKernelGGL(attn_rel_bwd_dq2_kernel<false>, grid, dim3(256), 0, s, p, rp, (const bf16*)dout, lse, ws,
-                         (bf16*)dqkv, part);
-    else
-      hipLaunchKernelGGL(attn_rel_bwd_dqs_kernel<false>, grid, dim3(256), 0, s, p, rp, (const bf16*)dsbuf, ldS,
-                         (bf16*)dqkv, part);
-  }
-  const size_t ds_bytes = ((size_t)p.B * p.H * p.T * ldS * sizeof(bf16) + 255) & ~(size_t)255;
-  float* dpos_part = reinterpret_cast<float*>(reinterpret_cast<char*>(dsbuf) + ds_bytes);
-  if (rel_vec(p, rp) && !(g_rel_mode & CFM_ATTN_MODE_REL_DPOS_R4)) {
-    const int nrt = cdiv(2 * p.T - 1, DP_R);
-    hipLaunchKernelGGL(attn_rel_bwd_dpos3_kernel, dim3(8 * cdiv(p.B * p.H, 8) * nrt), dim3(256), 0, s, p, rp,
-                       (const bf16*)dsbuf, ldS, dpos_part, nrt);
-  } else if (rel_vec(p, rp))
-    hipLaunchKernelGGL(attn_rel_bwd_dpos_kernel<true>, dim3(cdiv(2 * p.T - 1, TILE), p.H, p.B), dim3(256), 0, s, p, rp,
-                       (const bf16*)dsbuf, ldS, dpos_part);
-  else
-    hipLaunchKernelGGL(attn_rel_bwd_dpos_kernel<false>, dim3(cdiv(2 * p.T - 1, TILE), p.H, p.B), dim3(256), 0, s, p,
-                       rp, (const bf16*)dsbuf, ldS, dpos_part);
+    if (c.dpos == CFM_ATTN_DPOS_XCD) {
+      const int nrt = cdiv(nrel, DP_R);
+      hipLaunchKernelGGL(attn_rel_bwd_dpos3_kernel, dim3(8 * cdiv(B * H, 8) * nrt), dim3(256), 0, s, p, rp,
+                         (const bf16*)dsbuf, ldS, dpos_part, nrt);
+    } else
+      hipLaunchKernelGGL(attn_rel_bwd_dpos_kernel<VEC>, dim3(cdiv(nrel, TILE), H, B), dim3(256), 0, s, p, rp,
+                         (const bf16*)dsbuf, ldS, dpos_part);
+  });
   if (dpos_dt == CFM_BF16)   // the compute-dtype copy the dW_pos GEMM reads: no fp32 dpos + cast pass
-    colreduce_bf16(dpos_part, p.B, (long)(2 * p.T - 1) * p.HD, (bf16*)dpos, s);
+    colreduce_bf16(dpos_part, B, (long)nrel * p.HD, (bf16*)dpos, s);
   else
-    colreduce(dpos_part, p.B, (long)(2 * p.T - 1) * p.HD, (float*)dpos, 0, s);
-  const int nrows = p.B * 4 * cdiv(p.T, 128);
+    colreduce(dpos_part, B, (long)nrel * p.HD, (float*)dpos, 0, s);
+  const int nrows = B * 4 * cdiv(T, 128);
   colreduce_pair(part, part + p.HD, nrows, (long)p.HD, dpu, dpv, s, 2L * p.HD);   // du, dv: one launch
   return check_launch("cfm_attn_bwd(rel)");
 }

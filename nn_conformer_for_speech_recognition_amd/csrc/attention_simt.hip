@@ -10,7 +10,7 @@
 // One wavefront per query row (forward, dQ) or per key row (dK/dV) or per relative offset
 // (dpos); lanes run over keys for the scores and over the head dimension for the outputs.
 // The MFMA kernels (attention.hip) replace this path for bf16 without relative positions.
-#include "cfm_common.h"
+#include "attn_plan.h"   // the launcher prototypes; the plan sends fp32 and bf16 REL_SIMT here
 
 namespace {
 
@@ -230,8 +230,6 @@ int attn_simt_fwd_launch(const void* qkv, void* o, float* lse, const int32_t* le
   hipLaunchKernelGGL(attn_simt_fwd, dim3(cdiv(T, 4), H, B), dim3(256), 0, s, p, o, lse);
   return check_launch("cfm_attn_fwd(simt)");
 }
-
-size_t attn_simt_ws_bytes(int B, int T, int H) { return (size_t)B * H * T * T * sizeof(float); }
 
 int attn_simt_bwd_launch(const void* qkv, const void* o, const void* dout, const float* lse, const int32_t* len,
                          const void* pos, const float* pu, const float* pv, void* dqkv, float* dpos, float* dpu,

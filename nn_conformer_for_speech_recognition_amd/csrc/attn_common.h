@@ -2,13 +2,10 @@
 // tile geometry, the per-(b,h) parameter block, attention-dropout indexing, and the fragment
 // helpers that move 32x32x16 bf16 MFMA operands between LDS tiles, registers and accumulators.
 #pragma once
-#include "cfm_common.h"
+#include "attn_plan.h"   // DKP, KS, TILE: the tile geometry the plan sizes LDS by
 
 namespace {
 
-constexpr int DKP = 64;      // padded head dim
-constexpr int KS = DKP + 8;  // LDS row stride (elements): 144-B rows, conflict-free ds_read_b128
-constexpr int TILE = 64;     // keys (fwd/dQ) or queries (dK/dV) per LDS tile
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 
@@ -24,6 +21,13 @@ struct AttnM {
   bool vec4;   // 8-B vector loads legal (dk % 4 == 0, 8-B aligned rows: Conformer-S's dk 36)
   int qs;      // whole-head kernels: workgroups per (b, h), each a contiguous range of 32-row blocks (<= 1: one)
 };
+
+// the one place an AttnM is filled: vec, dbg, vec4 and qs as the plan chose them
+inline AttnM make_attnm(const cfm_attn_choice& c, const void* qkv, const int32_t* len, int B, int T, int H, int dk,
+                        float drop_p, uint64_t seed) {
+  return AttnM{(const bf16*)qkv, B, T, H, dk, 3 * H * dk, H * dk, len, 1.f / sqrtf((float)dk), drop_p, seed,
+               c.vec != 0, c.dbg, cfm::g_rng_salt, c.vec4 != 0, c.qs};
+}
 
 // attention-dropout element index: rows of an EVEN stride (T rounded up to even), so the keys 2m and
 // 2m+1 of one (query, key-pair) share one 32-bit hash (low / high 16 bits): kernels holding both keys of

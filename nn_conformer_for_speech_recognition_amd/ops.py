@@ -928,27 +928,26 @@ def attn_bwd(qkv, o, dout, lse, lengths_i32, B, T, H, dk, pos=None, pos_u=None, 
              D=None, ws=None, dpos_dtype=torch.float32):
     """D: optional (B*H*T,) fp32 rowsum(dO * O) per head, precomputed by the GEMM that produced dout
     (linear_dgrad(rowdot=...)); bf16 MFMA path only.  Rel-pos: D must be the head of ws (attn_ws).
+    ws: the library is told its byte size and lays it out for that size (cfm_attn_plan), so it is never overrun.
     dpos_dtype: torch.bfloat16 returns dpos already in the compute dtype (rel-pos MFMA path, cfm_attn_bwd_ex)."""
     rel = pos is not None
-    full = True     # ws is the whole cfm_attn_bwd_ws_bytes workspace (the non-rel whole-head path keeps dS^T there)
     if D is not None and ws is not None:
         if D.data_ptr() != ws.data_ptr():
             raise L.CfmError("attn_bwd: D must be the first B*H*T floats of ws")
     elif D is not None:
         if rel:
             raise L.CfmError("attn_bwd: rel-pos with a precomputed D needs its workspace (attn_ws)")
-        ws = D
-        full = False
-    else:
+        ws = D      # D alone: the library sees its size and runs the recomputing dQ kernel
+    elif ws is None:
         ws = workspace(L.size_call("cfm_attn_bwd_ws_bytes", B, T, H, dk, int(rel), L.dt(qkv)), qkv.device)
     dqkv = torch.empty_like(qkv)
     dpos = torch.empty(pos.shape, device=qkv.device, dtype=dpos_dtype) if rel else None
     dpu = torch.empty(H * dk, device=qkv.device, dtype=torch.float32) if rel else None
     dpv = torch.empty(H * dk, device=qkv.device, dtype=torch.float32) if rel else None
-    d_ready = (1 if D is not None else 0) | (2 if full else 0)
     L.call("cfm_attn_bwd_ex", L.ptr(qkv), L.ptr(o), L.ptr(dout), L.ptr(lse), L.ptr(lengths_i32), L.ptr(pos),
            L.ptr(pos_u), L.ptr(pos_v), L.ptr(dqkv), L.ptr(dpos), L.dt(dpos), L.ptr(dpu), L.ptr(dpv), B, T, H, dk,
-           L.dt(qkv), float(drop_p), int(seed) & (2**64 - 1), d_ready, L.ptr(ws), L.stream())
+           L.dt(qkv), float(drop_p), int(seed) & (2**64 - 1), int(D is not None), L.ptr(ws),
+           ws.numel() * ws.element_size(), L.stream())
     return dqkv, dpos, dpu, dpv
 
 

@@ -161,10 +161,12 @@ def _header_enum(name):
 @pytest.mark.parametrize("enum,cprefix,pyprefix", [
     ("cfm_gemm_mode", "CFM_GEMM_MODE_", "GEMM_MODE_"), ("cfm_gemm_sel", "CFM_GEMM_SEL_", "GEMM_SEL_"),
     ("cfm_gemm_variant", "CFM_GEMM_V_", "GEMM_V_"), ("cfm_gemm_epilogue", "CFM_GEMM_EPI_", "GEMM_EPI_"),
-    ("cfm_attn_mode", "CFM_ATTN_MODE_", "ATTN_MODE_")])
+    ("cfm_attn_mode", "CFM_ATTN_MODE_", "ATTN_MODE_"), ("cfm_attn_path", "CFM_ATTN_PATH_", "ATTN_PATH_"),
+    ("cfm_attn_dpos", "CFM_ATTN_DPOS_", "ATTN_DPOS_"), ("cfm_attn_ws", "CFM_ATTN_WS_", "ATTN_WS_")])
 def test_python_constants_mirror_the_header(enum, cprefix, pyprefix):
     hdr = _header_enum(enum)
-    assert len(hdr) >= 5 and all(k.startswith(cprefix) for k in hdr)
+    assert len(hdr) >= (4 if enum in ("cfm_attn_path", "cfm_attn_dpos", "cfm_attn_ws") else 5)
+    assert all(k.startswith(cprefix) for k in hdr)
     mirror = {cprefix + k[len(pyprefix):]: v for k, v in vars(L).items() if k.startswith(pyprefix) and isinstance(v, int)}
     assert mirror == hdr
     if enum == "cfm_gemm_mode":

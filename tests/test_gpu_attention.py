@@ -102,7 +102,8 @@ def test_attention_kernels_agree_under_dropout(attn_mode):
 
 def test_rowdot_epilogue_feeds_attention_bwd():
     """D = rowsum(dO * O) per head from the out-projection dgrad GEMM's epilogue (cfm_gemm_desc.rowdot_*)
-    equals the separate D pass, and cfm_attn_bwd_with_d reproduces cfm_attn_bwd."""
+    equals the separate D pass, and cfm_attn_bwd_ex with d_ready = 1 (that D as its whole workspace) reproduces
+    d_ready = 0, which computes D itself."""
     B, T, H, dk = 3, 97, 8, 64
     g = torch.Generator().manual_seed(21)
     qkv = torch.randn(B * T, 3 * H * dk, generator=g).to(DEV, torch.bfloat16)
@@ -291,3 +292,115 @@ def test_rel_dpos_bf16_output_is_the_cast():
         assert torch.equal(got[1], ops.cast(ref[1], torch.bfloat16))
         for a, b in zip((got[0], got[2], got[3]), (ref[0], ref[2], ref[3])):
             assert torch.equal(a, b)
+
+
+# ------------------------------------------------------------------------------------ the sized backward workspace
+BAND = 256                                   # guard floats on each side of the workspace (1 KiB: offsets stay 256-aligned)
+PATTERN = -7.25
+
+
+def _guarded(nbytes):
+    """(buffer, workspace view of exactly nbytes) with BAND patterned floats before and behind the view"""
+    assert nbytes % 4 == 0
+    buf = torch.full((2 * BAND + nbytes // 4,), PATTERN, device=DEV)
+    return buf, buf[BAND:BAND + nbytes // 4]
+
+
+def _bands_untouched(buf):
+    return bool((buf[:BAND] == PATTERN).all()) and bool((buf[-BAND:] == PATTERN).all())
+
+
+def _ws_bytes(B, T, H, dk, rel, dtype):
+    return _lib.size_call("cfm_attn_bwd_ws_bytes", B, T, H, dk, int(rel), _lib.dt(torch.empty(0, dtype=dtype)))
+
+
+def _case(B, T, H, dk, lens, seed, dtype=torch.bfloat16, rel=False):
+    g = torch.Generator().manual_seed(seed)
+    qkv = torch.randn(B * T, 3 * H * dk, generator=g).to(DEV, dtype)
+    do = torch.randn(B * T, H * dk, generator=g).to(DEV, dtype)
+    pos = (0.5 * torch.randn(2 * T - 1, H * dk, generator=g)).to(DEV, dtype) if rel else None
+    pu = (0.3 * torch.randn(H * dk, generator=g)).to(DEV) if rel else None
+    pv = (0.3 * torch.randn(H * dk, generator=g)).to(DEV) if rel else None
+    return qkv, do, torch.tensor(lens, dtype=torch.int32, device=DEV), pos, pu, pv
+
+
+def _rowdot(do, o, B, T, H, dk):
+    return (do.float() * o.float()).view(B, T, H, dk).sum(-1).permute(0, 2, 1).reshape(-1).contiguous()
+
+
+@pytest.mark.parametrize("B,T,H,dk,lens,dtype,rel,mode", [
+    (2, 97, 2, 64, [97, 40], torch.bfloat16, False, 0),                               # whole-head, stored dS
+    (2, 130, 2, 36, [130, 65], torch.bfloat16, False, 0),
+    (2, 97, 2, 64, [97, 40], torch.bfloat16, False, _lib.ATTN_MODE_DQ_RECOMPUTE),     # whole-head, recompute
+    (2, 130, 2, 36, [130, 65], torch.bfloat16, False, _lib.ATTN_MODE_DQ_RECOMPUTE),
+    (1, 385, 1, 64, [385], torch.bfloat16, False, 0),                                 # tiled
+    (2, 130, 2, 64, [130, 65], torch.bfloat16, False, _lib.ATTN_MODE_TILED),
+    (2, 130, 2, 64, [130, 1], torch.bfloat16, True, 0),                               # rel, vectorised
+    (2, 97, 2, 36, [97, 60], torch.bfloat16, True, 0),                                # rel, zero-filling loads
+    (1, 37, 2, 16, [37], torch.float32, False, 0),                                    # SIMT
+    (1, 37, 2, 16, [37], torch.float32, True, 0),
+])
+def test_bwd_stays_inside_its_workspace(attn_mode, B, T, H, dk, lens, dtype, rel, mode):
+    """The backward given exactly cfm_attn_bwd_ws_bytes inside a larger tensor: the patterned bands before and
+    behind the workspace are untouched and every output is finite, one small case per path (sizes that cross a
+    32-row block, a 64-key tile and an odd T)."""
+    attn_mode(mode)
+    qkv, do, ln, pos, pu, pv = _case(B, T, H, dk, lens, 31 + T + dk, dtype, rel)
+    buf, ws = _guarded(_ws_bytes(B, T, H, dk, rel, dtype))
+    o, lse = ops.attn_fwd(qkv, ln, B, T, H, dk, pos, pu, pv, drop_p=0.1, seed=7)
+    outs = ops.attn_bwd(qkv, o, do, lse, ln, B, T, H, dk, pos, pu, pv, drop_p=0.1, seed=7, ws=ws)
+    torch.cuda.synchronize()
+    assert _bands_untouched(buf)
+    assert torch.isfinite(o.float()).all()
+    for t in outs[:4 if rel else 1]:
+        assert torch.isfinite(t.float()).all()
+
+
+def test_d_only_workspace_runs_the_recomputing_dq(attn_mode):
+    """D precomputed and nothing behind it: the size tells the library that dS^T has no room, so the recomputing dQ
+    kernel runs -- bit for bit the ATTN_MODE_DQ_RECOMPUTE run on a full workspace -- and the band behind D is
+    untouched.  Four bytes less is an argument error before any launch: dqkv keeps its pattern."""
+    B, T, H, dk = 2, 97, 2, 64
+    n = B * H * T
+    qkv, do, ln, _, _, _ = _case(B, T, H, dk, [97, 40], 5)
+    o, lse = ops.attn_fwd(qkv, ln, B, T, H, dk, drop_p=0.1, seed=7)
+    Dv = _rowdot(do, o, B, T, H, dk)
+    full, Dfull = ops.attn_ws(B, T, H, dk, False, DEV)
+    assert full.numel() * 4 == 132864 > n * 4                # mode 0: D slot + dS^T
+    Dfull.copy_(Dv)
+    attn_mode(_lib.ATTN_MODE_DQ_RECOMPUTE)
+    want = ops.attn_bwd(qkv, o, do, lse, ln, B, T, H, dk, drop_p=0.1, seed=7, D=Dfull, ws=full)[0]
+    attn_mode(0)
+    buf, ws = _guarded(n * 4)
+    ws.copy_(Dv)
+    got = ops.attn_bwd(qkv, o, do, lse, ln, B, T, H, dk, drop_p=0.1, seed=7, D=ws, ws=ws)[0]
+    torch.cuda.synchronize()
+    assert _bands_untouched(buf)
+    assert torch.isfinite(got.float()).all() and torch.equal(got, want)
+    # too small: B*H*T*4 - 4 bytes
+    dqkv = torch.full_like(qkv, 3.5)
+    with pytest.raises(_lib.CfmError, match=str(n * 4)):
+        _lib.call("cfm_attn_bwd_ex", _lib.ptr(qkv), _lib.ptr(o), _lib.ptr(do), _lib.ptr(lse), _lib.ptr(ln), None, None,
+                  None, _lib.ptr(dqkv), None, _lib.F32, None, None, B, T, H, dk, _lib.BF16, 0.1, 7, 1, _lib.ptr(ws),
+                  n * 4 - 4, _lib.stream())
+    torch.cuda.synchronize()
+    assert bool((dqkv == 3.5).all()) and _bands_untouched(buf)
+
+
+def test_mode_change_between_sizing_and_launch(attn_mode):
+    """A workspace sized under ATTN_MODE_DQ_RECOMPUTE (D alone) and launched under mode 0, which would otherwise keep
+    dS^T behind D: the byte count wins, the guard is untouched, and the result is the recompute run's."""
+    B, T, H, dk = 2, 97, 2, 64
+    qkv, do, ln, _, _, _ = _case(B, T, H, dk, [97, 40], 6)
+    o, lse = ops.attn_fwd(qkv, ln, B, T, H, dk, drop_p=0.1, seed=7)
+    attn_mode(_lib.ATTN_MODE_DQ_RECOMPUTE)
+    nbytes = _ws_bytes(B, T, H, dk, False, torch.bfloat16)
+    assert nbytes == B * H * T * 4
+    want = ops.attn_bwd(qkv, o, do, lse, ln, B, T, H, dk, drop_p=0.1, seed=7)[0]
+    attn_mode(0)
+    assert _ws_bytes(B, T, H, dk, False, torch.bfloat16) > nbytes
+    buf, ws = _guarded(nbytes)
+    got = ops.attn_bwd(qkv, o, do, lse, ln, B, T, H, dk, drop_p=0.1, seed=7, ws=ws)[0]
+    torch.cuda.synchronize()
+    assert _bands_untouched(buf)
+    assert torch.equal(got, want)

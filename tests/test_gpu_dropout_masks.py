@@ -400,7 +400,7 @@ def _check_attn(T, dk, lens, seed, rel, mask_seed=None, dtype=BF):
 @pytest.mark.parametrize("seed", [9, WIDE])
 def test_attention_masks_past_one_key_tile(attn_mode, mode, T, dk, lens, seed):
     """Three key tiles with a ragged second utterance (kt * TILE enters didx); odd T (the T_even row stride); dk 36.
-    The whole-head kernels split these B H = 4 heads over 3-4 workgroups each (head_split); ATTN_MODE_REL_ZERO_FILL
+    The whole-head kernels split these B H = 4 heads over 3-4 workgroups each (the plan's qs); ATTN_MODE_REL_ZERO_FILL
     keeps one workgroup per head, the split a full-size batch gets."""
     attn_mode(mode)
     _check_attn(T, dk, lens, seed, rel=False)
