@@ -563,7 +563,8 @@ enum cfm_attn_mode {
   CFM_ATTN_MODE_REL_ZERO_FILL = 1 << 6,   /* keeps the rel-pos kernels' zero-filling tile loads; one forward row block */
   CFM_ATTN_MODE_REL_DPOS_R4 = 1 << 7,     /* keeps the round-4 rel-pos dpos kernel */
   CFM_ATTN_MODE_REL_DQ_RECOMPUTE = 1 << 9, /* keeps the recomputing rel-pos dQ2 kernel (default: dQ from the stored dS) */
-  CFM_ATTN_MODE_DQ_RECOMPUTE = 1 << 10    /* keeps the recomputing whole-head dQ kernel (default: the stored dS) */
+  CFM_ATTN_MODE_DQ_RECOMPUTE = 1 << 10,   /* keeps the recomputing whole-head dQ kernel (default: the stored dS) */
+  CFM_ATTN_MODE_DKDV_TWO_PASS = 1 << 11   /* keeps the two-pass whole-head dK/dV kernel (default: one sweep) */
 };
 int cfm_attn_set_mode(int mode);
 

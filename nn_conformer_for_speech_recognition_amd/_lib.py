@@ -99,6 +99,7 @@ ATTN_MODE_REL_ZERO_FILL = 1 << 6
 ATTN_MODE_REL_DPOS_R4 = 1 << 7
 ATTN_MODE_REL_DQ_RECOMPUTE = 1 << 9
 ATTN_MODE_DQ_RECOMPUTE = 1 << 10
+ATTN_MODE_DKDV_TWO_PASS = 1 << 11
 # cfm_attn_path / cfm_attn_dpos / cfm_attn_ws (cfm_attn_plan)
 ATTN_PATH_SIMT, ATTN_PATH_HEAD, ATTN_PATH_TILED, ATTN_PATH_REL = range(4)
 ATTN_DPOS_NONE, ATTN_DPOS_XCD, ATTN_DPOS_R4_VEC, ATTN_DPOS_R4 = range(4)

@@ -379,6 +379,7 @@ __device__ __forceinline__ void store_acc_rows(const f32x16& a0, const f32x16& a
   }
 }
 
+// (the two-pass form, kept behind CFM_ATTN_MODE_DKDV_TWO_PASS; the default is attn_bwd_dkdv_sweep_kernel below)
 // dK, dV, one wave per 32-key block: grid (B*H), block 64 * ceil(T/32) (three waves per SIMD at
 // T = 373); the head's whole Q and dO (and lse, D) are staged once and every wave sweeps 32-query
 // steps over them with no further barriers.  Two passes keep every wave under the three-wave register
@@ -550,9 +551,146 @@ __global__ __launch_bounds__(64 * HEAD_TMAX / 32) void attn_bwd_dkdv_wave_kernel
   }
 }
 
+// dK, dV in one sweep: the same staging, work split, dropout indexing and dS^T layout as the two-pass kernel above, but
+// every 32-query step forms S, P and the keep mask once and feeds both accumulator pairs from them: dV^T += dO^T (P mask),
+// dP = dO V^T, dS = P (mask keep dP - D), dK^T += Q^T dS (16 MFMAs, 16 exponentials and 16 fragment reads per step
+// instead of 20 / 32 / 20; no keep bits through LDS -- the sM bytes of the plan's lds_dkdv stay unused).  Every value is
+// produced by the same operations in the same order as in the two passes, so dV, dK and dS^T are bit-identical to them.
+// Registers: the four accumulators (64), the K and V fragments (32), S/P and dP (32) and the packed P and dS (16) fit
+// under the three-wave cap with nothing spilled (DESIGN.md section 8j has the compiler's report) -- as long as the lse / D
+// rows of only one register group are in flight: DROP is a template parameter so that the step is one basic block and the
+// scheduling barriers between the groups hold (behind a run-time dropout branch the compiler sank all four groups'
+// arithmetic below all eight row loads and spilled).
+template <bool DROP>
+__global__ __launch_bounds__(64 * HEAD_TMAX / 32) void attn_bwd_dkdv_sweep_kernel(AttnM p, const bf16* __restrict__ dout,
+                                                                                  const float* __restrict__ lse,
+                                                                                  const float* __restrict__ Dg,
+                                                                                  bf16* __restrict__ dqkv,
+                                                                                  bf16* __restrict__ dsT) {
+  constexpr bool drop = DROP;
+  if (drop) p.seed = salted_seed(p.seed, p.salt);
+  const uint32_t dkey = drop_key(p.seed, 0), dthr = drop_thr(p.drop_p);
+  const float dkeep = drop_keep_scale(dthr);
+  extern __shared__ __attribute__((aligned(16))) bf16 hsm[];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, hh = lane >> 5;
+  const HeadPart hp = head_part(p);
+  const int b = hp.b, h = hp.h;
+  const int len = p.len[b];
+  const int nq = (p.T + 31) / 32, Tq = nq * 32;
+  bf16* sQall = hsm;
+  bf16* sGall = hsm + (long)Tq * KS;
+  float* sL = reinterpret_cast<float*>(sGall + (long)Tq * KS);      // [Tq] lse * log2(e) (+inf past T)
+  float* sD = sL + Tq;                                              // [Tq] D
+  const bf16* qbase = p.qkv + (long)b * p.T * p.D3 + h * p.dk;
+  head_stage(p, qbase, dout + (long)b * p.T * p.HD + h * p.dk, p.D3, p.HD, Tq, sQall, sGall, tid, blockDim.x);
+  for (int i = tid; i < Tq; i += blockDim.x) {
+    sL[i] = i < p.T ? lse[((long)b * p.H + h) * p.T + i] * LOG2E : INFINITY;
+    sD[i] = i < p.T ? Dg[((long)b * p.H + h) * p.T + i] : 0.f;
+  }
+  const int k0w = (hp.blk0 + wv) * 32;
+  const int kj = k0w + (lane & 31);
+  const bool kvalid = kj < len;
+  bf16x8 kf[4], vf[4];
+  load_bfrags(p, qbase + p.HD, p.D3, kj, p.T, kf, lane);
+  load_bfrags(p, qbase + 2 * p.HD, p.D3, kj, p.T, vf, lane);
+  __syncthreads();
+  const float c = p.scale * LOG2E;
+  const int nqs = k0w < len ? nq : 0;      // key blocks past len: zero gradients
+  const int odd = lane & 1, sh = 16 * odd;
+  const uint32_t T2 = (uint32_t)(p.T + (p.T & 1)) >> 1;
+  const uint32_t hbase = ((uint32_t)(b * p.H + h) * (uint32_t)p.T + (uint32_t)(4 * hh + odd)) * T2 + (uint32_t)(kj >> 1);
+  bf16* obase = dqkv + (long)b * p.T * p.D3 + h * p.dk;
+  const int nvalid = min(32, p.T - k0w);
+  const bool v8 = p.vec && ((uintptr_t)dqkv & 7) == 0;
+  const float keep = drop ? dkeep : 1.f;
+  bf16* drow0 = dsT ? dsT + ((long)(b * p.H + h) * Tq + kj) * Tq + 16 * hh : nullptr;
+
+  f32x16 dv0 = (f32x16){0}, dv1 = (f32x16){0}, dk0 = (f32x16){0}, dk1 = (f32x16){0};
+  auto sg = [&](int qt, f32x16& sa, f32x16& ga) {
+    sa = (f32x16){0};
+    ga = (f32x16){0};
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4)
+      sa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rowfrag(sQall, qt * 32, 16 * s4, lane), kf[s4], sa, 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4)
+      ga = __builtin_amdgcn_mfma_f32_32x32x16_bf16(rowfrag(sGall, qt * 32, 16 * s4, lane), vf[s4], ga, 0, 0, 0);
+  };
+  auto acc = [&](int qt, const f32x16& sa, const f32x16& ga) {
+    const int q0 = qt * 32;
+    bf16x8 pf[2], sf[2];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {          // registers 4g .. 4g+3 = queries q0 + 8g + 4hh + 0..3
+      const float4 Lg = *reinterpret_cast<const float4*>(sL + q0 + 8 * g + 4 * hh);
+      const float4 Dq = *reinterpret_cast<const float4*>(sD + q0 + 8 * g + 4 * hh);
+      const float Lr[4] = {Lg.x, Lg.y, Lg.z, Lg.w}, Dr[4] = {Dq.x, Dq.y, Dq.z, Dq.w};
+      bool kp[4] = {true, true, true, true};
+      if (drop) {
+#pragma unroll
+        for (int e = 0; e < 4; e += 2) {
+          // (the wave-uniform offset through readfirstlane: otherwise the per-register bases are
+          // hoisted out of the loop as VGPRs)
+          const uint32_t hm = attn_mix(hbase + dkey + __builtin_amdgcn_readfirstlane((q0 + 8 * g + e) * (int)T2));
+          const uint32_t ho = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hm, 0xB1, 0xF, 0xF, false);  // lane ^ 1
+          const uint32_t h0 = odd ? ho : hm, h1 = odd ? hm : ho;
+          kp[e] = ((h0 >> sh) & 0xFFFFu) >= dthr;
+          kp[e + 1] = ((h1 >> sh) & 0xFFFFu) >= dthr;
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int r = 4 * g + e;
+        const float pa = fast_exp2(__builtin_fmaf(sa[r], c, -Lr[e]));   // lse = +inf for q >= T
+        const float mk = drop ? (kp[e] ? dkeep : 0.f) : 1.f;
+        const float gk = kp[e] ? ga[r] : 0.f;
+        pf[r >> 3][r & 7] = (bf16)(pa * mk);
+        sf[r >> 3][r & 7] = (bf16)(pa * __builtin_fmaf(gk, keep, -Dr[e]));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (!kvalid) pf[0] = pf[1] = sf[0] = sf[1] = (bf16x8){0};     // keys past len: P = dS = 0
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+      dv0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(trfrag_perm(sGall, q0 + 16 * s2, 0, lane), pf[s2], dv0, 0, 0, 0);
+      dv1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(trfrag_perm(sGall, q0 + 16 * s2, 32, lane), pf[s2], dv1, 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (dsT) {
+      // Registers 4g .. 4g+3 = queries q0 + 8g + 4hh + 0..3 of key kj: a key's 32 queries sit in eight 8-byte pieces
+      // over its two lanes (hh = 0, 1).  Swapping dwords between the wave's halves (group g of the upper half against
+      // group g + 2 of the lower) leaves lane (kj, 0) with queries q0 .. q0 + 15 and lane (kj, 1) with q0 + 16 .. + 31,
+      // so the same bytes go out as two 16-byte stores per lane instead of four 8-byte ones.
+      const uint4 x = __builtin_bit_cast(uint4, sf[0]), y = __builtin_bit_cast(uint4, sf[1]);
+      typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+      const u32x2 r0 = __builtin_amdgcn_permlane32_swap(x.x, y.x, false, false);
+      const u32x2 r1 = __builtin_amdgcn_permlane32_swap(x.y, y.y, false, false);
+      const u32x2 r2 = __builtin_amdgcn_permlane32_swap(x.z, y.z, false, false);
+      const u32x2 r3 = __builtin_amdgcn_permlane32_swap(x.w, y.w, false, false);
+      bf16* drow = drow0 + q0;
+      *reinterpret_cast<uint4*>(drow) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
+      *reinterpret_cast<uint4*>(drow + 8) = make_uint4(r2[0], r3[0], r2[1], r3[1]);
+    }
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+      dk0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(trfrag_perm(sQall, q0 + 16 * s2, 0, lane), sf[s2], dk0, 0, 0, 0);
+      dk1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(trfrag_perm(sQall, q0 + 16 * s2, 32, lane), sf[s2], dk1, 0, 0, 0);
+    }
+  };
+  f32x16 sa, ga;
+  for (int qt = 0; qt < nqs; ++qt) {
+    sg(qt, sa, ga);
+    __builtin_amdgcn_sched_barrier(0);
+    acc(qt, sa, ga);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  store_acc_rows(dv0, dv1, 1.f, obase + 2 * p.HD, p.D3, k0w, nvalid, p.dk, v8, lane);
+  store_acc_rows(dk0, dk1, p.scale, obase + p.HD, p.D3, k0w, nvalid, p.dk, v8, lane);
+}
+
 // ------------------------------------------------------------------------------------ dQ from the stored dS^T
 // (round 6 default on the whole-head path when the caller passes the full workspace; CFM_ATTN_MODE_DQ_RECOMPUTE keeps
-// attn_bwd_dq_head_kernel).  dq_i = scale * sum_j dS_ij k_j over the dS^T that attn_bwd_dkdv_wave_kernel stored:
+// attn_bwd_dq_head_kernel).  dq_i = scale * sum_j dS_ij k_j over the dS^T that the dK/dV kernel (one sweep or two passes) stored:
 // 8 MFMAs per 64-key tile and wave, no score / softmax / dropout-hash / dO x V recompute.  Whole-head layout like the
 // other head kernels: grid (B*H*qs), one wave per 32-query block; the head's K is staged once (192-B rows: the
 // transposed fragment reads are conflict free), then each wave streams its [64 keys][32 queries] dS^T slices through
@@ -902,7 +1040,8 @@ CFM_EXPORT int cfm_attn_bwd_ex(const void* qkv, const void* o, const void* dout,
   CFM_REQUIRE(!pos || (pos_u && pos_v && dpos && dpos_u && dpos_v), CFM_ERR_ARG, "rel-pos grads need buffers");
   CFM_REQUIRE(ws_bytes <= (size_t)INT64_MAX, CFM_ERR_ARG, "ws_bytes");
   cfm_attn_choice c;
-  if (const int rc = attn_plan(attn_query(qkv, dout, pos, B, T, H, dk, dtype, (int64_t)ws_bytes), c, __func__)) return rc;
+  const cfm_attn_query q = attn_query(qkv, dout, pos, B, T, H, dk, dtype, (int64_t)ws_bytes);
+  if (const int rc = attn_plan(q, c, __func__)) return rc;
   const bool mfma = c.path != CFM_ATTN_PATH_SIMT;
   CFM_REQUIRE(!d_ready || mfma, CFM_ERR_UNSUPPORTED, "precomputed D: bf16 MFMA path only");
   CFM_REQUIRE(dpos_dt == CFM_F32 || (dpos_dt == CFM_BF16 && pos && mfma), CFM_ERR_DTYPE,
@@ -929,7 +1068,11 @@ CFM_EXPORT int cfm_attn_bwd_ex(const void* qkv, const void* o, const void* dout,
   // whole-head: dK/dV (which stores dS^T where the plan gave it a section), then dQ from it or recomputed
   const dim3 grid(B * H * c.qs), block(64 * c.waves);
   bf16* dsT = c.dq_stored ? attn_ws_ptr<bf16>(c, CFM_ATTN_WS_DS, ws) : nullptr;
-  hipLaunchKernelGGL(attn_bwd_dkdv_wave_kernel, grid, block, c.lds_dkdv, s, p, (const bf16*)dout, lse, D, (bf16*)dqkv, dsT);
+  // (one sweep; CFM_ATTN_MODE_DKDV_TWO_PASS keeps the two-pass kernel: same plan, same LDS, same results)
+  hipLaunchKernelGGL((q.mode & CFM_ATTN_MODE_DKDV_TWO_PASS) ? attn_bwd_dkdv_wave_kernel
+                     : drop_p > 0.f                          ? attn_bwd_dkdv_sweep_kernel<true>
+                                                             : attn_bwd_dkdv_sweep_kernel<false>,
+                     grid, block, c.lds_dkdv, s, p, (const bf16*)dout, lse, D, (bf16*)dqkv, dsT);
   if (dsT)
     hipLaunchKernelGGL(attn_bwd_dqs_head_kernel, grid, block, c.lds_dqs, s, p, (const bf16*)dsT, (bf16*)dqkv);
   else
