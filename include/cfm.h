@@ -371,7 +371,7 @@ int cfm_layernorm_fwd_mx_ex(const void* x, int dtype_x, const float* gamma, cons
 int cfm_layernorm_fwd_res(const float* x, const void* delta, int dtype_d, float* xout, const float* gamma,
                           const float* beta, void* y, int dtype_y, void* y8, uint8_t* s8, float* mean, float* rstd,
                           long M, int D, float eps, void* stream);
-size_t cfm_layernorm_ws_bytes(long M, int D);
+size_t cfm_layernorm_ws_bytes(long M, int D);   /* (blocks + 1) * 8*D bytes (cfm_layernorm_plan); 0 for a refused D / M */
 int cfm_layernorm_bwd(const void* dy, int dtype_dy, const void* x, int dtype_x, const float* gamma,
                       const float* mean, const float* rstd, const void* dres, int dtype_dres,
                       void* dx, int dtype_dx, float* dgamma, float* dbeta, float* ws, long M, int D,
@@ -393,18 +393,61 @@ int cfm_layernorm_bwd_drop(const void* dy, int dtdy, const void* x, int dtx, con
    reduce -- nb = ws_bytes / (16*D) rows of 2*D floats for the first pair at ws, the same for the second at
    ws + nb*2*D.
    cfm_layernorm_pair_ok: 1 when fused kernels exist for width D and dtype_z (D 512, 256, and the lane-group widths
-   D % 8 == 0, D < 512, D != 128), else 0 -- then make the two calls; pure host logic, no GPU API.  All pointers 16-B
-   aligned. */
+   D % 8 == 0, D < 512, D != 128), else 0 -- then make the two calls; pure host logic, no GPU API (cfm_layernorm_plan
+   of a CFM_LN_FWD_PAIR query).  All pointers 16-B aligned (CFM_ERR_ALIGN otherwise). */
 int cfm_layernorm_pair_ok(int D, int dtype_z);
 size_t cfm_layernorm_fwd_pair_ws_bytes(long M, int D);   /* 0: the forward needs no workspace */
 int cfm_layernorm_fwd_pair(const float* x, const float* gamma1, const float* beta1, const float* gamma2,
                            const float* beta2, float* y, void* z, int dtype_z, float* mean1, float* rstd1,
                            float* mean2, float* rstd2, long M, int D, float eps, void* stream);
-size_t cfm_layernorm_bwd_pair_ws_bytes(long M, int D);
+size_t cfm_layernorm_bwd_pair_ws_bytes(long M, int D);   /* 0 where cfm_layernorm_pair_ok(D, ...) is 0 */
 int cfm_layernorm_bwd_pair(const void* dz, int dtype_dz, const float* dres, const float* x, const float* gamma1,
                            const float* beta1, const float* mean1, const float* rstd1, const float* gamma2,
                            const float* mean2, const float* rstd2, float* dx, float* dgb1, float* dgb2, float* ws,
                            long M, int D, void* g2, float g2_scale, float g2_p, uint64_t g2_seed, void* stream);
+
+/* What the LayerNorm entry points above launch, as a pure host function (csrc/ln_plan.h): every cfm_layernorm_* call,
+   cfm_layernorm_ws_bytes, cfm_layernorm_bwd_pair_ws_bytes and cfm_layernorm_pair_ok act on this one rule. */
+enum cfm_ln_op {
+  CFM_LN_FWD = 0,                         /* cfm_layernorm_fwd, cfm_layernorm_fwd_mx(_ex) (want_mx) */
+  CFM_LN_FWD_RES = 1,                     /* cfm_layernorm_fwd_res */
+  CFM_LN_BWD = 2,                         /* cfm_layernorm_bwd, cfm_layernorm_bwd_drop (want_g2) */
+  CFM_LN_FWD_PAIR = 3,
+  CFM_LN_BWD_PAIR = 4
+};
+enum cfm_ln_family {
+  CFM_LN_GENERIC = 0,                     /* any D <= 1024, any alignment: one wave per row, 4-byte strided elements */
+  CFM_LN_WAVE = 1,                        /* D = 64 * width: one wave per row, width features per lane */
+  CFM_LN_GROUP = 2                        /* D % 8 == 0, D <= 512: width lanes per row, 8 features per lane */
+};
+typedef struct {
+  int op;                                 /* cfm_ln_op */
+  int D;
+  int64_t M;
+  /* dtype codes of the operands the op has (the others are ignored): x; y (pair: z); dy (pair: dz); dx; dres
+     (CFM_F32 when there is none); fwd_res's delta */
+  int dt_x, dt_y, dt_dy, dt_dx, dt_dres, dt_delta;
+  /* the pointers' addresses modulo 16, 0 for the ones the op does not have or that are NULL.  gamma / beta: the
+     (first) LayerNorm's; gamma2 / beta2: the pair's second; y: the pair's fp32 y, z its second output */
+  int x_mod16, y_mod16, z_mod16, gamma_mod16, beta_mod16, gamma2_mod16, beta2_mod16;
+  int delta_mod16, xout_mod16, y8_mod16;  /* fwd_res: delta, xout; the MX copy's y8 */
+  int dy_mod16, dres_mod16, dx_mod16, g2_mod16;
+  int want_mx;                            /* forward: also y's MX e4m3 copy (y8, s8) */
+  int want_g2;                            /* backward: also g2 = bf16(dx * scale * dropout) */
+} cfm_ln_query;
+typedef struct {
+  int family;                             /* cfm_ln_family */
+  int width;                              /* WAVE: V = D / 64 in {2, 4, 8, 16}; GROUP: G in {16, 32, 64}; GENERIC: 0 */
+  int g2_fused;                           /* g2 written by the LayerNorm kernel; 0: a cfm_scale_dropout pass over dx */
+  int blocks;                             /* workgroups (of 256 threads) of the LayerNorm kernel */
+  size_t ws_bytes;                        /* backward workspace (cfm_layernorm_ws_bytes / _bwd_pair_ws_bytes); forward 0 */
+} cfm_ln_choice;
+/* Calls no GPU API.  CFM_ERR_ARG for a null pointer or an unknown op; otherwise the code the entry point returns for
+   the same input before it launches anything: CFM_ERR_DTYPE for a y / z / dy / dz (delta, the MX forward's x) that is
+   neither CFM_F32 nor CFM_BF16, CFM_ERR_SHAPE for D outside (0, 1024], M < 0, an MX copy off D in {256, 512, 1024} /
+   bf16 y, or a pair width without fused kernels, CFM_ERR_ALIGN for an MX copy or a pair with a pointer off 16 bytes.
+   The single-LayerNorm entry points never fail on alignment or x / dx / dres dtypes: such calls run GENERIC. */
+int cfm_layernorm_plan(const cfm_ln_query* q, cfm_ln_choice* out);
 
 /* y = act(x*scale [dropout]) + residual, elementwise helpers used at residual joins. */
 int cfm_scale_dropout(const void* x, int dtype_x, void* y, int dtype_y, long n, float scale,

@@ -119,6 +119,25 @@ class AttnChoice(ctypes.Structure):
         ("ws_off", c_size_t * 4), ("ws_size", c_size_t * 4), ("ws_total", c_size_t)]
 
 
+# cfm_ln_op / cfm_ln_family (cfm_layernorm_plan)
+LN_FWD, LN_FWD_RES, LN_BWD, LN_FWD_PAIR, LN_BWD_PAIR = range(5)
+LN_GENERIC, LN_WAVE, LN_GROUP = range(3)
+
+
+class LnQuery(ctypes.Structure):
+    """cfm_ln_query (include/cfm.h): one LayerNorm call as cfm_layernorm_plan reads it."""
+    _fields_ = [("op", c_int), ("D", c_int), ("M", ctypes.c_int64)] + [(n, c_int) for n in (
+        "dt_x", "dt_y", "dt_dy", "dt_dx", "dt_dres", "dt_delta",
+        "x_mod16", "y_mod16", "z_mod16", "gamma_mod16", "beta_mod16", "gamma2_mod16", "beta2_mod16",
+        "delta_mod16", "xout_mod16", "y8_mod16", "dy_mod16", "dres_mod16", "dx_mod16", "g2_mod16",
+        "want_mx", "want_g2")]
+
+
+class LnChoice(ctypes.Structure):
+    """cfm_ln_choice (include/cfm.h)."""
+    _fields_ = [(n, c_int) for n in ("family", "width", "g2_fused", "blocks")] + [("ws_bytes", c_size_t)]
+
+
 class ConvmodQuery(ctypes.Structure):
     """cfm_convmod_query (include/cfm.h): one conv-module launch as cfm_convmod_plan reads it."""
     _fields_ = [("op", c_int), ("norm", c_int), ("dtype_a", c_int), ("dtype_da", c_int), ("dtype_dz", c_int),
@@ -208,6 +227,7 @@ _SIGS = {
     "cfm_layernorm_bwd_drop": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p,
                                        c_float, c_float, c_u64, c_void_p]),
+    "cfm_layernorm_plan": (c_int, [ctypes.POINTER(LnQuery), ctypes.POINTER(LnChoice)]),
     "cfm_layernorm_pair_ok": (c_int, [c_int, c_int]),
     "cfm_layernorm_fwd_pair_ws_bytes": (c_size_t, [c_long, c_int]),
     "cfm_layernorm_fwd_pair": (c_int, [c_void_p] * 7 + [c_int] + [c_void_p] * 4 + [c_long, c_int, c_float, c_void_p]),

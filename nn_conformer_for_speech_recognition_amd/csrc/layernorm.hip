@@ -5,12 +5,15 @@
 // fp32; the normalised output feeds the next GEMM in the compute dtype (bf16 or fp32).
 // Backward fuses the residual-gradient add (dx = LN'(dy) + dres) and produces dgamma/dbeta
 // through per-workgroup partial rows reduced by cfm::colreduce (deterministic, no atomics).
-// Fast path (D = 64*V, fp32 residual stream): each lane owns V contiguous features, so every
-// load/store is a 16-B vector; other shapes/dtypes take the generic strided path.
-#include "cfm_common.h"
+// Fast kernels (D = 64*V: one wave per row; other D % 8 == 0: a lane group per row): each lane owns contiguous
+// features, so every load/store is a 16-B vector; other shapes/dtypes take the generic strided kernels.  Which one
+// serves a call is ln_plan's answer (ln_plan.h); the entry points at the end of this file only act on it.
+#include <type_traits>
+
+#include "ln_plan.h"
 
 namespace {
-constexpr int MAXJ = 16;   // D <= 1024
+constexpr int MAXJ = LN_DMAX / 64;   // registers per lane that hold a row of the generic kernels
 
 // ---------------------------------------------------------------- vector helpers (V per lane)
 template <int V> __device__ __forceinline__ void ldv(const float* p, float (&o)[V]) {
@@ -72,10 +75,7 @@ template <int V> __device__ __forceinline__ void stv(bf16* p, const float (&v)[V
   }
 }
 
-// ---------------------------------------------------------------- vectorised kernels
-// LN_FWD_ROWS rows per wave: every row's load is issued before the first reduction, so a wave keeps
-// that many 2-KB row reads in flight (one row per wave left the kernel latency-bound at ~50 % of HBM)
-constexpr int LN_FWD_ROWS = 2;
+// ---------------------------------------------------------------- optional operands of the fast kernels
 // MX: a second output of the bf16 y -- its MX e4m3 copy (cfm_quant_mx's bytes and block scales of the bf16 values,
 // for the fp8 forward GEMM that consumes it): the 32 / V lanes of a 32-feature block exchange their maxima by xor
 // shuffles, so the copy costs its 1.03 bytes per element of stores instead of a separate 3-byte pass.
@@ -123,67 +123,6 @@ struct LnRes {
   float* xo;       // M x D: x + delta
 };
 
-template <int V, typename TY, bool MX = false, typename TX = float, bool RS = false>
-__global__ __launch_bounds__(256) void ln_fwd_vec(const TX* __restrict__ x, const float* __restrict__ gamma,
-                                                  const float* __restrict__ beta, TY* __restrict__ y,
-                                                  float* __restrict__ mean_out, float* __restrict__ rstd_out, long M,
-                                                  float eps, LnMx mx = {}, LnRes rs = {}) {
-  constexpr int D = 64 * V, R = LN_FWD_ROWS;
-  const int lane = threadIdx.x & 63;
-  const long row0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * R;
-  if (row0 >= M) return;
-  float v[R][V], g[V], b[V];
-  [[maybe_unused]] float dl[RS ? R : 1][RS ? V : 1];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    if (row0 + r < M) {
-      ldv<V>(x + (row0 + r) * D + lane * V, v[r]);
-      if constexpr (RS) ldv<V>(rs.d + (row0 + r) * D + lane * V, dl[r]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < V; ++i) v[r][i] = 0.f;
-      if constexpr (RS) {
-#pragma unroll
-        for (int i = 0; i < V; ++i) dl[r][i] = 0.f;
-      }
-    }
-  }
-  if constexpr (RS) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-#pragma unroll
-      for (int i = 0; i < V; ++i) v[r][i] += dl[r][i];
-      if (row0 + r < M) stv<V>(rs.xo + (row0 + r) * D + lane * V, v[r]);
-    }
-  }
-  ldv<V>(gamma + lane * V, g);
-  ldv<V>(beta + lane * V, b);
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < V; ++i) s += v[r][i];
-    const float mean = wave_sum(s) * (1.f / D);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < V; ++i) {
-      v[r][i] -= mean;
-      q += v[r][i] * v[r][i];
-    }
-    const float rstd = rsqrtf(wave_sum(q) * (1.f / D) + eps);
-    if (row0 + r < M) {    // wave-uniform
-#pragma unroll
-      for (int i = 0; i < V; ++i) v[r][i] = v[r][i] * rstd * g[i] + b[i];
-      stv<V>(y + (row0 + r) * D + lane * V, v[r]);
-      if constexpr (MX) ln_store_mx<V>(mx, row0 + r, D, lane, v[r]);
-      if (lane == 0) {
-        mean_out[row0 + r] = mean;
-        rstd_out[row0 + r] = rstd;
-      }
-    }
-  }
-}
-
 // optional fused second output of the vectorised backward: g2 = bf16(dx * scale * dropout(p, seed))
 struct LnDrop {
   void* g2;
@@ -192,103 +131,186 @@ struct LnDrop {
   const uint64_t* salt;
 };
 
-template <int V, typename TDY, typename TX = float>
-__global__ __launch_bounds__(256) void ln_bwd_vec(const TDY* __restrict__ dy, const TX* __restrict__ x,
-                                                  const float* __restrict__ gamma, const float* __restrict__ mean_in,
-                                                  const float* __restrict__ rstd_in, const float* __restrict__ dres,
-                                                  float* __restrict__ dx, float* __restrict__ ws, long M, LnDrop dr) {
-  if (dr.g2 && dr.p > 0.f) dr.seed = salted_seed(dr.seed, dr.salt);
-  constexpr int D = 64 * V;
-  __shared__ float red[4][2 * D];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int wglob = blockIdx.x * 4 + wv;
-  const int nwaves = gridDim.x * 4;
-  float gm[V], pg[V], pb[V];
-  ldv<V>(gamma + lane * V, gm);
+// ---------------------------------------------------------------- row geometry
+// How the 64 lanes of a wave share rows; the fast kernels are written once over a Geom.
+//   F, RPW, LDSW   features per lane (contiguous: 16-B vectors), rows per wave and trip, columns of an LDS partial row
+//   D(), inv_d()   the row width and 1 / D
+//   col(), act()   the lane's first column; whether the lane holds columns of the row at all
+//   sub()          the lane's row slot inside its wave (0 .. RPW - 1)
+//   leader()       the lane that writes its row's statistics
+//   heads()        the lanes whose column partials go to LDS, after fold() summed the wave's row slots into them
+//   sum(v)         v summed over the lanes of the row
+// RowWave<V>: one wave per row, D = 64 V at compile time, every lane active.  kEarlyExit: a forward wave whose rows
+// all lie past M returns at once (its shuffles span one row, nobody waits for it).
+template <int V> struct RowWave {
+  static constexpr int F = V, RPW = 1, LDSW = 64 * V;
+  static constexpr bool kWave = true, kEarlyExit = true, kReloadY = false;
+  int lane;
+  __device__ __forceinline__ RowWave(int lane_, int) : lane(lane_) {}
+  __device__ __forceinline__ int D() const { return 64 * V; }
+  __device__ __forceinline__ float inv_d() const { return 1.f / (64 * V); }
+  __device__ __forceinline__ int col() const { return lane * V; }
+  __device__ __forceinline__ bool act() const { return true; }
+  __device__ __forceinline__ int sub() const { return 0; }
+  __device__ __forceinline__ bool leader() const { return lane == 0; }
+  __device__ __forceinline__ bool heads() const { return true; }
+  __device__ __forceinline__ float sum(float v) const { return wave_sum(v); }
+  __device__ __forceinline__ void fold(float (&)[F]) const {}
+};
+// RowGroup<G>: widths that are not 64 * V (Conformer-S: D = 144) on 16-B vectors: a group of G lanes owns one row, 8
+// contiguous features per lane (lanes 8 j >= D idle), 64 / G rows per wave, the row sums over the group by xor
+// shuffles inside it.  (The strided generic kernels below moved 4-B elements with per-element dtype branches: 20 us
+// per D-144 backward where the bytes take ~5.)  The shuffles span the wave, so every group runs the same trips and
+// rows past M are masked, never skipped.
+// kReloadY: the pair forward's second LayerNorm takes y as the single forward does: 16-B loads (of this lane's own
+// stores just above, from the cache -- still no pass over memory) through a pointer the compiler cannot trace back to
+// them.  Fed from the registers it contracts (v - sum / D) and the squares differently per element than the single
+// forward, and rstd2 comes out an ulp off the two-call path.
+template <int G_> struct RowGroup {
+  static constexpr int G = G_, F = 8, RPW = 64 / G_, LDSW = 8 * G_;
+  static constexpr bool kWave = false, kEarlyExit = false, kReloadY = true;
+  int lane, d, c;
+  bool a;
+  float invd;
+  __device__ __forceinline__ RowGroup(int lane_, int D_)
+      : lane(lane_), d(D_), c(8 * (lane_ % G_)), a(8 * (lane_ % G_) < D_), invd(1.f / (float)D_) {}
+  __device__ __forceinline__ int D() const { return d; }
+  __device__ __forceinline__ float inv_d() const { return invd; }
+  __device__ __forceinline__ int col() const { return c; }
+  __device__ __forceinline__ bool act() const { return a; }
+  __device__ __forceinline__ int sub() const { return lane / G; }
+  __device__ __forceinline__ bool leader() const { return lane % G == 0; }
+  __device__ __forceinline__ bool heads() const { return lane < G; }
+  __device__ __forceinline__ float sum(float v) const {
 #pragma unroll
-  for (int i = 0; i < V; ++i) pg[i] = pb[i] = 0.f;
-  for (long row = wglob; row < M; row += nwaves) {
-    const float mean = mean_in[row], rstd = rstd_in[row];
-    float d[V], xh[V], g[V];
-    ldv<V>(dy + row * D + lane * V, d);
-    ldv<V>(x + row * D + lane * V, xh);
-    float sg = 0.f, sgx = 0.f;
+    for (int o = 1; o < G; o <<= 1) v += __shfl_xor(v, o, 64);
+    return v;
+  }
+  // the groups of a wave hold the same columns: xor over the group index bits
+  __device__ __forceinline__ void fold(float (&p)[F]) const {
 #pragma unroll
-    for (int i = 0; i < V; ++i) {
-      xh[i] = (xh[i] - mean) * rstd;
-      g[i] = d[i] * gm[i];
-      pg[i] += d[i] * xh[i];
-      pb[i] += d[i];
-      sg += g[i];
-      sgx += g[i] * xh[i];
-    }
-    sg = wave_sum(sg) * (1.f / D);
-    sgx = wave_sum(sgx) * (1.f / D);
-    float o[V];
-    if (dres) ldv<V>(dres + row * D + lane * V, o);
-    else {
+    for (int o = G; o < 64; o <<= 1) {
 #pragma unroll
-      for (int i = 0; i < V; ++i) o[i] = 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < V; ++i) o[i] += rstd * (g[i] - sg - xh[i] * sgx);
-    stv<V>(dx + row * D + lane * V, o);
-    if constexpr (V == 8) {
-      if (dr.g2) {   // the next module's input gradient: bf16(dx * scale * dropout mask), as cfm_scale_dropout
-        float sc[8];
-        if (dr.p > 0.f) dropout_scale8(dr.p, dr.seed, (uint64_t)(row * D + lane * V), sc);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) sc[i] = dr.p > 0.f ? dr.scale * sc[i] : dr.scale;
-        float q[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) q[i] = o[i] * sc[i];
-        st8_dyn(dr.g2, CFM_BF16, row * D + lane * V, q);
-      }
+      for (int i = 0; i < F; ++i) p[i] += __shfl_xor(p[i], o, 64);
     }
   }
+};
+
+template <int N> __device__ __forceinline__ void ln_zero(float (&v)[N]) {
 #pragma unroll
-  for (int i = 0; i < V; ++i) {
-    red[wv][lane * V + i] = pg[i];
-    red[wv][D + lane * V + i] = pb[i];
+  for (int i = 0; i < N; ++i) v[i] = 0.f;
+}
+
+// ---------------------------------------------------------------- shared row code
+// What the kernels below share beyond the geometry.  How far this goes is set by the bit-identity the tests hold the
+// kernels to (the pair against two calls, every kernel against its recorded outputs): the compiler decides per
+// instruction mix which multiplies it packs in pairs and which it contracts into fmas, and moving a row's arithmetic
+// behind a function boundary moves those decisions.  Measured on this file: the forward's statistics written as a
+// function over the row (by reference or per element by value) contract the lane-group kernels' squares and shift
+// rstd by an ulp; the pair backward on ln_bwd_stage / ln_write_partials fuses one more multiply-add per stage.  So
+// ln_fwd and ln_fwd_pair spell the same row statements out (two copies, one per kernel, for both geometries), the
+// pair backward kernels spell out their two stages and their write-out, and the helpers here serve the rest.
+
+// the LN_FWD_ROWS rows of a lane from row0 on, zero where the lane or the row is outside
+template <typename Geom, typename T>
+__device__ __forceinline__ void ln_load_rows(const Geom& geo, const T* p, long row0, long M,
+                                             float (&v)[LN_FWD_ROWS][Geom::F]) {
+#pragma unroll
+  for (int r = 0; r < LN_FWD_ROWS; ++r) {
+    if (geo.act() && row0 + r < M) ldv<Geom::F>(p + (row0 + r) * geo.D() + geo.col(), v[r]);
+    else ln_zero(v[r]);
+  }
+}
+// One LayerNorm backward stage over a lane's features of one row.  d: the gradient of the stage's output, h: its
+// normalised input, gam: its weight.  Adds the row to the column partials (pg += d h, pb += d), leaves g = d gam and
+// the row means s1 = mean(g), s2 = mean(g h); the stage's input gradient is then ln_bwd_term per element.
+template <typename Geom>
+__device__ __forceinline__ void ln_bwd_stage(const Geom& geo, const float (&d)[Geom::F], const float (&h)[Geom::F],
+                                             const float (&gam)[Geom::F], float (&g)[Geom::F], float (&pg)[Geom::F],
+                                             float (&pb)[Geom::F], float& s1, float& s2) {
+  float a = 0.f, b = 0.f;
+#pragma unroll
+  for (int i = 0; i < Geom::F; ++i) {
+    g[i] = d[i] * gam[i];
+    pg[i] += d[i] * h[i];
+    pb[i] += d[i];
+    a += g[i];
+    b += g[i] * h[i];
+  }
+  s1 = geo.sum(a) * geo.inv_d();
+  s2 = geo.sum(b) * geo.inv_d();
+}
+__device__ __forceinline__ float ln_bwd_term(float rstd, float g, float s1, float h, float s2) {
+  return rstd * (g - s1 - h * s2);
+}
+
+// g2 of a lane's 8 features at element idx: the next module's input gradient bf16(dx * scale * dropout mask), as
+// cfm_scale_dropout makes it from dx.  Only the 8-feature geometries have it (ln_plan: g2_fused).
+template <typename Geom>
+__device__ __forceinline__ void ln_store_g2(const LnDrop& dr, long idx, const float (&o)[Geom::F]) {
+  if constexpr (Geom::F == 8) {
+    if (dr.g2) {
+      float sc[8];
+      if (dr.p > 0.f) dropout_scale8(dr.p, dr.seed, (uint64_t)idx, sc);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) sc[i] = dr.p > 0.f ? dr.scale * sc[i] : dr.scale;
+      float q[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) q[i] = o[i] * sc[i];
+      st8_dyn(dr.g2, CFM_BF16, idx, q);
+    }
+  }
+}
+
+// A workgroup's column partials [pg | pb] (already folded) summed over its four waves through LDS into row `blk` of
+// ws (2 D floats).
+template <typename Geom>
+__device__ __forceinline__ void ln_write_partials(const Geom& geo, float (&red)[4][2 * Geom::LDSW],
+                                                  const float (&pg)[Geom::F], const float (&pb)[Geom::F], float* ws,
+                                                  long blk) {
+  const int D = geo.D(), c = geo.col(), wv = threadIdx.x >> 6;
+  if (geo.heads()) {
+#pragma unroll
+    for (int i = 0; i < Geom::F; ++i) {
+      red[wv][c + i] = pg[i];
+      red[wv][Geom::LDSW + c + i] = pb[i];
+    }
   }
   __syncthreads();
-  for (int c = threadIdx.x; c < 2 * D; c += 256)
-    ws[(long)blockIdx.x * 2 * D + c] = red[0][c] + red[1][c] + red[2][c] + red[3][c];
+  for (int q = threadIdx.x; q < 2 * D; q += 256) {
+    const int k = q < D ? q : Geom::LDSW + (q - D);
+    ws[blk * 2 * D + q] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
+  }
 }
 
-// ---------------------------------------------------------------- lane-group kernels (D % 8 == 0, D <= 8 G)
-// Widths that are not 64 * V (Conformer-S: D = 144) on 16-B vectors: a group of G lanes owns one row, 8 contiguous
-// features per lane (lanes 8 j >= D idle), 64 / G rows per wave, the row sums over the group by xor shuffles inside
-// it.  (The strided generic kernels below moved 4-B elements with per-element dtype branches: 20 us per D-144
-// backward where the bytes take ~5.)
-template <int G> __device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = 1; o < G; o <<= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-template <int G, typename TY, typename TX = float, bool RS = false>
-__global__ __launch_bounds__(256) void ln_fwd_grp(const TX* __restrict__ x, const float* __restrict__ gamma,
-                                                  const float* __restrict__ beta, TY* __restrict__ y,
-                                                  float* __restrict__ mean_out, float* __restrict__ rstd_out, long M,
-                                                  int D, float eps, LnRes rs = {}) {
-  constexpr int RPW = 64 / G, R = LN_FWD_ROWS;
-  const int lane = threadIdx.x & 63, j = lane % G, c = 8 * j;
-  const bool act = c < D;
-  const long row0 = (((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + lane / G) * R;
-  float v[R][8], g[8], b[8];
-  [[maybe_unused]] float dl[RS ? R : 1][8];
+// ---------------------------------------------------------------- forward
+// LN_FWD_ROWS rows per wave (RowWave) or lane group (RowGroup).  MX (RowWave, V >= 4, bf16 y): also y's MX copy.
+// RS: x + delta (cfm_layernorm_fwd_res).
+template <typename Geom, typename TY, bool MX = false, typename TX = float, bool RS = false>
+__global__ __launch_bounds__(256) void ln_fwd(const TX* __restrict__ x, const float* __restrict__ gamma,
+                                              const float* __restrict__ beta, TY* __restrict__ y,
+                                              float* __restrict__ mean_out, float* __restrict__ rstd_out, long M,
+                                              int D_, float eps, LnMx mx, LnRes rs) {
+  constexpr int F = Geom::F, R = LN_FWD_ROWS;
+  const Geom geo(threadIdx.x & 63, D_);
+  const int D = geo.D(), c = geo.col();
+  const long row0 = (((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * Geom::RPW + geo.sub()) * R;
+  if constexpr (Geom::kEarlyExit) {
+    if (row0 >= M) return;
+  }
+  float v[R][F], g[F], b[F];
+  [[maybe_unused]] float dl[RS ? R : 1][RS ? F : 1];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    if (act && row0 + r < M) {
-      ldv<8>(x + (row0 + r) * D + c, v[r]);
-      if constexpr (RS) ldv<8>(rs.d + (row0 + r) * D + c, dl[r]);
+    if (geo.act() && row0 + r < M) {
+      ldv<F>(x + (row0 + r) * D + c, v[r]);
+      if constexpr (RS) ldv<F>(rs.d + (row0 + r) * D + c, dl[r]);
     } else {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) v[r][i] = 0.f;
+      for (int i = 0; i < F; ++i) v[r][i] = 0.f;
       if constexpr (RS) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) dl[r][i] = 0.f;
+        for (int i = 0; i < F; ++i) dl[r][i] = 0.f;
       }
     }
   }
@@ -296,63 +318,166 @@ __global__ __launch_bounds__(256) void ln_fwd_grp(const TX* __restrict__ x, cons
 #pragma unroll
     for (int r = 0; r < R; ++r) {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) v[r][i] += dl[r][i];
-      if (act && row0 + r < M) stv<8>(rs.xo + (row0 + r) * D + c, v[r]);
+      for (int i = 0; i < F; ++i) v[r][i] += dl[r][i];
+      if (geo.act() && row0 + r < M) stv<F>(rs.xo + (row0 + r) * D + c, v[r]);
     }
   }
-  if (act) {
-    ldv<8>(gamma + c, g);
-    ldv<8>(beta + c, b);
+  if (geo.act()) {
+    ldv<F>(gamma + c, g);
+    ldv<F>(beta + c, b);
   }
-  const float invd = 1.f / (float)D;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) s += v[r][i];
-    const float mean = group_sum<G>(s) * invd;
+    for (int i = 0; i < F; ++i) s += v[r][i];
+    const float mean = geo.sum(s) * geo.inv_d();
     float q = 0.f;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      v[r][i] = act ? v[r][i] - mean : 0.f;
+    for (int i = 0; i < F; ++i) {
+      v[r][i] = geo.act() ? v[r][i] - mean : 0.f;
       q += v[r][i] * v[r][i];
     }
-    const float rstd = rsqrtf(group_sum<G>(q) * invd + eps);
-    if (row0 + r < M) {
-      if (act) {
+    const float rstd = rsqrtf(geo.sum(q) * geo.inv_d() + eps);
+    if (row0 + r < M) {    // (RowWave: wave-uniform)
+      if (geo.act()) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) v[r][i] = v[r][i] * rstd * g[i] + b[i];
-        stv<8>(y + (row0 + r) * D + c, v[r]);
+        for (int i = 0; i < F; ++i) v[r][i] = v[r][i] * rstd * g[i] + b[i];
+        stv<F>(y + (row0 + r) * D + c, v[r]);
       }
-      if (j == 0) {
+      if (geo.leader()) {
         mean_out[row0 + r] = mean;
         rstd_out[row0 + r] = rstd;
+      }
+      if constexpr (MX) ln_store_mx<F>(mx, row0 + r, D, geo.lane, v[r]);
+    }
+  }
+}
+
+// ---------------------------------------------------------------- LayerNorm pairs (layer boundary)
+// final_layer_norm of encoder layer i followed directly by the ffn1 LayerNorm of layer i + 1: y = LN(x; g1, b1) is the
+// fp32 stream between the layers, z = LN(y; g2, b2) the next layer's first GEMM operand.  One kernel per direction
+// instead of two: the forward keeps y in registers (no fp32 write-then-read), the backward recomputes y from x and
+// never materialises the gradient of y.  Each pass is ln_fwd's row arithmetic statement for statement, which is what
+// makes y, z and the statistics equal the two-call path's bit for bit (a row past M stays all zero through both).
+template <typename Geom, typename TZ>
+__global__ __launch_bounds__(256) void ln_fwd_pair(const float* __restrict__ x, const float* __restrict__ gamma1,
+                                                   const float* __restrict__ beta1, const float* __restrict__ gamma2,
+                                                   const float* __restrict__ beta2, float* __restrict__ y,
+                                                   TZ* __restrict__ z, float* __restrict__ mean1,
+                                                   float* __restrict__ rstd1, float* __restrict__ mean2,
+                                                   float* __restrict__ rstd2, long M, int D_, float eps) {
+  constexpr int F = Geom::F, R = LN_FWD_ROWS;
+  const Geom geo(threadIdx.x & 63, D_);
+  const int D = geo.D(), c = geo.col();
+  const long row0 = (((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * Geom::RPW + geo.sub()) * R;
+  if constexpr (Geom::kEarlyExit) {
+    if (row0 >= M) return;
+  }
+  float v[R][F], g[F], b[F];
+  ln_load_rows(geo, x, row0, M, v);
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    if constexpr (Geom::kReloadY) {
+      if (pass) {
+        const float* yr = y;
+        asm volatile("" : "+s"(yr) : : "memory");
+        ln_load_rows(geo, yr, row0, M, v);
+      }
+    }
+    if (geo.act()) {
+      ldv<F>((pass ? gamma2 : gamma1) + c, g);
+      ldv<F>((pass ? beta2 : beta1) + c, b);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < F; ++i) s += v[r][i];
+      const float mean = geo.sum(s) * geo.inv_d();
+      float q = 0.f;
+#pragma unroll
+      for (int i = 0; i < F; ++i) {
+        v[r][i] = geo.act() ? v[r][i] - mean : 0.f;
+        q += v[r][i] * v[r][i];
+      }
+      const float rstd = rsqrtf(geo.sum(q) * geo.inv_d() + eps);
+      if (row0 + r < M) {
+        if (geo.act()) {
+#pragma unroll
+          for (int i = 0; i < F; ++i) v[r][i] = v[r][i] * rstd * g[i] + b[i];
+          if (pass == 0) stv<F>(y + (row0 + r) * D + c, v[r]);
+          else stv<F>(z + (row0 + r) * D + c, v[r]);
+        }
+        if (geo.leader()) {
+          (pass ? mean2 : mean1)[row0 + r] = mean;
+          (pass ? rstd2 : rstd1)[row0 + r] = rstd;
+        }
       }
     }
   }
 }
 
-template <int G, typename TDY, typename TX = float>
-__global__ __launch_bounds__(256) void ln_bwd_grp(const TDY* __restrict__ dy, const TX* __restrict__ x,
-                                                  const float* __restrict__ gamma, const float* __restrict__ mean_in,
-                                                  const float* __restrict__ rstd_in, const float* __restrict__ dres,
-                                                  float* __restrict__ dx, float* __restrict__ ws, long M, int D,
-                                                  LnDrop dr) {
+// ---------------------------------------------------------------- backward
+// dx = dres + LN'(dy), the column partials [dgamma | dbeta] = [dy xh | dy] to row blockIdx.x of ws.  One row per wave
+// and trip.
+template <typename Geom, typename TDY, typename TX = float>
+__global__ __launch_bounds__(256) void ln_bwd_wave(const TDY* __restrict__ dy, const TX* __restrict__ x,
+                                                   const float* __restrict__ gamma, const float* __restrict__ mean_in,
+                                                   const float* __restrict__ rstd_in, const float* __restrict__ dres,
+                                                   float* __restrict__ dx, float* __restrict__ ws, long M, LnDrop dr) {
+  static_assert(Geom::kWave, "one row per wave");
   if (dr.g2 && dr.p > 0.f) dr.seed = salted_seed(dr.seed, dr.salt);
-  constexpr int RPW = 64 / G;
-  __shared__ float red[4][2 * 8 * G];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane % G, c = 8 * j;
-  const bool act = c < D;
-  const long slot = ((long)blockIdx.x * 4 + wv) * RPW + lane / G;
-  const long nslots = (long)gridDim.x * 4 * RPW;
-  float gm[8], pg[8], pb[8];
+  constexpr int F = Geom::F;
+  __shared__ float red[4][2 * Geom::LDSW];
+  const Geom geo(threadIdx.x & 63, 0);
+  const int D = geo.D(), c = geo.col();
+  const int wglob = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int nwaves = gridDim.x * 4;
+  float gm[F], pg[F], pb[F];
+  ldv<F>(gamma + c, gm);
+  ln_zero(pg);
+  ln_zero(pb);
+  for (long row = wglob; row < M; row += nwaves) {
+    const float mean = mean_in[row], rstd = rstd_in[row];
+    float d[F], xh[F], g[F], sg, sgx;
+    ldv<F>(dy + row * D + c, d);
+    ldv<F>(x + row * D + c, xh);
 #pragma unroll
-  for (int i = 0; i < 8; ++i) gm[i] = pg[i] = pb[i] = 0.f;
+    for (int i = 0; i < F; ++i) xh[i] = (xh[i] - mean) * rstd;
+    ln_bwd_stage(geo, d, xh, gm, g, pg, pb, sg, sgx);
+    float o[F];
+    if (dres) ldv<F>(dres + row * D + c, o);
+    else ln_zero(o);
+#pragma unroll
+    for (int i = 0; i < F; ++i) o[i] += ln_bwd_term(rstd, g[i], sg, xh[i], sgx);
+    stv<F>(dx + row * D + c, o);
+    ln_store_g2<Geom>(dr, row * D + c, o);
+  }
+  ln_write_partials(geo, red, pg, pb, ws, blockIdx.x);
+}
+
+template <typename Geom, typename TDY, typename TX = float>
+__global__ __launch_bounds__(256) void ln_bwd_group(const TDY* __restrict__ dy, const TX* __restrict__ x,
+                                                    const float* __restrict__ gamma, const float* __restrict__ mean_in,
+                                                    const float* __restrict__ rstd_in, const float* __restrict__ dres,
+                                                    float* __restrict__ dx, float* __restrict__ ws, long M, int D,
+                                                    LnDrop dr) {
+  static_assert(!Geom::kWave, "a lane group per row");
+  if (dr.g2 && dr.p > 0.f) dr.seed = salted_seed(dr.seed, dr.salt);
+  __shared__ float red[4][2 * Geom::LDSW];
+  const Geom geo(threadIdx.x & 63, D);
+  const int c = geo.col();
+  const bool act = geo.act();
+  const long slot = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * Geom::RPW + geo.sub();
+  const long nslots = (long)gridDim.x * 4 * Geom::RPW;
+  float gm[8], pg[8], pb[8];
+  ln_zero(gm);
+  ln_zero(pg);
+  ln_zero(pb);
   if (act) ldv<8>(gamma + c, gm);
-  const float invd = 1.f / (float)D;
-  // every group of the wave runs the same trip count (the shuffles span the wave); rows past M are masked.  Two rows
-  // per group and iteration, all their loads issued before the first reduction (one row at a time left the kernel
-  // latency-bound: 9.4 us per D-144 backward for ~28 MB)
+  // two rows per group and iteration, all their loads issued before the first reduction (one row at a time left the
+  // kernel latency-bound: 9.4 us per D-144 backward for ~28 MB)
   const long nrow_iter = (M + nslots - 1) / nslots;
   for (long it = 0; it < nrow_iter; it += 2) {
     long row[2];
@@ -377,243 +502,74 @@ __global__ __launch_bounds__(256) void ln_bwd_grp(const TDY* __restrict__ dy, co
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      float g[8], sg = 0.f, sgx = 0.f;
+      float g[8], sg, sgx;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        xh[u][i] = live[u] ? (xh[u][i] - mean[u]) * rstd[u] : 0.f;
-        g[i] = d[u][i] * gm[i];
-        pg[i] += d[u][i] * xh[u][i];
-        pb[i] += d[u][i];
-        sg += g[i];
-        sgx += g[i] * xh[u][i];
-      }
-      sg = group_sum<G>(sg) * invd;
-      sgx = group_sum<G>(sgx) * invd;
+      for (int i = 0; i < 8; ++i) xh[u][i] = live[u] ? (xh[u][i] - mean[u]) * rstd[u] : 0.f;
+      ln_bwd_stage(geo, d[u], xh[u], gm, g, pg, pb, sg, sgx);
       if (live[u]) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) o[u][i] += rstd[u] * (g[i] - sg - xh[u][i] * sgx);
+        for (int i = 0; i < 8; ++i) o[u][i] += ln_bwd_term(rstd[u], g[i], sg, xh[u][i], sgx);
         stv<8>(dx + row[u] * D + c, o[u]);
-        if (dr.g2) {   // the next module's input gradient: bf16(dx * scale * dropout mask), as cfm_scale_dropout
-          float sc[8];
-          if (dr.p > 0.f) dropout_scale8(dr.p, dr.seed, (uint64_t)(row[u] * D + c), sc);
-#pragma unroll
-          for (int i = 0; i < 8; ++i) sc[i] = dr.p > 0.f ? dr.scale * sc[i] : dr.scale;
-          float q[8];
-#pragma unroll
-          for (int i = 0; i < 8; ++i) q[i] = o[u][i] * sc[i];
-          st8_dyn(dr.g2, CFM_BF16, row[u] * D + c, q);
-        }
+        ln_store_g2<Geom>(dr, row[u] * D + c, o[u]);
       }
     }
   }
-  // the groups of a wave hold the same columns: fold them (xor over the group index bits), then group 0 writes
-#pragma unroll
-  for (int o = G; o < 64; o <<= 1) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      pg[i] += __shfl_xor(pg[i], o, 64);
-      pb[i] += __shfl_xor(pb[i], o, 64);
-    }
-  }
-  if (lane < G) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      red[wv][c + i] = pg[i];
-      red[wv][8 * G + c + i] = pb[i];
-    }
-  }
-  __syncthreads();
-  for (int q = threadIdx.x; q < 2 * D; q += 256) {
-    const int k = q < D ? q : 8 * G + (q - D);
-    ws[(long)blockIdx.x * 2 * D + q] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-  }
-}
-
-// ---------------------------------------------------------------- LayerNorm pairs (layer boundary)
-// final_layer_norm of encoder layer i followed directly by the ffn1 LayerNorm of layer i + 1: y = LN(x; g1, b1) is the
-// fp32 stream between the layers, z = LN(y; g2, b2) the next layer's first GEMM operand.  One kernel per direction
-// instead of two: the forward keeps y in registers (no fp32 write-then-read), the backward recomputes y from x and
-// never materialises the gradient of y.  The expressions and the reduction order are those of ln_fwd_vec /
-// ln_fwd_grp, so y, z and the statistics equal the two-call path's bit for bit.
-template <int V, typename TZ>
-__global__ __launch_bounds__(256) void ln_fwd_pair_vec(const float* __restrict__ x, const float* __restrict__ gamma1,
-                                                       const float* __restrict__ beta1,
-                                                       const float* __restrict__ gamma2,
-                                                       const float* __restrict__ beta2, float* __restrict__ y,
-                                                       TZ* __restrict__ z, float* __restrict__ mean1,
-                                                       float* __restrict__ rstd1, float* __restrict__ mean2,
-                                                       float* __restrict__ rstd2, long M, float eps) {
-  constexpr int D = 64 * V, R = LN_FWD_ROWS;
-  const int lane = threadIdx.x & 63;
-  const long row0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * R;
-  if (row0 >= M) return;
-  float v[R][V], g[V], b[V];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    if (row0 + r < M) {
-      ldv<V>(x + (row0 + r) * D + lane * V, v[r]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < V; ++i) v[r][i] = 0.f;
-    }
-  }
-#pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {
-    ldv<V>((pass ? gamma2 : gamma1) + lane * V, g);
-    ldv<V>((pass ? beta2 : beta1) + lane * V, b);
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      float s = 0.f;
-#pragma unroll
-      for (int i = 0; i < V; ++i) s += v[r][i];
-      const float mean = wave_sum(s) * (1.f / D);
-      float q = 0.f;
-#pragma unroll
-      for (int i = 0; i < V; ++i) {
-        v[r][i] -= mean;
-        q += v[r][i] * v[r][i];
-      }
-      const float rstd = rsqrtf(wave_sum(q) * (1.f / D) + eps);
-      if (row0 + r < M) {    // wave-uniform (a row past M stays all zero through both passes)
-#pragma unroll
-        for (int i = 0; i < V; ++i) v[r][i] = v[r][i] * rstd * g[i] + b[i];
-        if (pass == 0) stv<V>(y + (row0 + r) * D + lane * V, v[r]);
-        else stv<V>(z + (row0 + r) * D + lane * V, v[r]);
-        if (lane == 0) {
-          (pass ? mean2 : mean1)[row0 + r] = mean;
-          (pass ? rstd2 : rstd1)[row0 + r] = rstd;
-        }
-      }
-    }
-  }
-}
-
-template <int G, typename TZ>
-__global__ __launch_bounds__(256) void ln_fwd_pair_grp(const float* __restrict__ x, const float* __restrict__ gamma1,
-                                                       const float* __restrict__ beta1,
-                                                       const float* __restrict__ gamma2,
-                                                       const float* __restrict__ beta2, float* __restrict__ y,
-                                                       TZ* __restrict__ z, float* __restrict__ mean1,
-                                                       float* __restrict__ rstd1, float* __restrict__ mean2,
-                                                       float* __restrict__ rstd2, long M, int D, float eps) {
-  constexpr int RPW = 64 / G, R = LN_FWD_ROWS;
-  const int lane = threadIdx.x & 63, j = lane % G, c = 8 * j;
-  const bool act = c < D;
-  const long row0 = (((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + lane / G) * R;
-  float v[R][8], g[8], b[8];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    if (act && row0 + r < M) {
-      ldv<8>(x + (row0 + r) * D + c, v[r]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v[r][i] = 0.f;
-    }
-  }
-  const float invd = 1.f / (float)D;
-#pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {
-    if (pass) {
-      // the second LayerNorm takes y as ln_fwd_grp does: 16-B loads (of this lane's own stores just above, from the
-      // cache -- still no pass over memory) through a pointer the compiler cannot trace back to them.  Fed from the
-      // registers it contracts (v - sum / D) and the squares differently per element than ln_fwd_grp, and rstd2
-      // comes out an ulp off the two-call path
-      const float* yr = y;
-      asm volatile("" : "+s"(yr) : : "memory");
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        if (act && row0 + r < M) {
-          ldv<8>(yr + (row0 + r) * D + c, v[r]);
-        } else {
-#pragma unroll
-          for (int i = 0; i < 8; ++i) v[r][i] = 0.f;
-        }
-      }
-    }
-    if (act) {
-      ldv<8>((pass ? gamma2 : gamma1) + c, g);
-      ldv<8>((pass ? beta2 : beta1) + c, b);
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      float s = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) s += v[r][i];
-      const float mean = group_sum<G>(s) * invd;
-      float q = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        v[r][i] = act ? v[r][i] - mean : 0.f;
-        q += v[r][i] * v[r][i];
-      }
-      const float rstd = rsqrtf(group_sum<G>(q) * invd + eps);
-      if (row0 + r < M) {
-        if (act) {
-#pragma unroll
-          for (int i = 0; i < 8; ++i) v[r][i] = v[r][i] * rstd * g[i] + b[i];
-          if (pass == 0) stv<8>(y + (row0 + r) * D + c, v[r]);
-          else stv<8>(z + (row0 + r) * D + c, v[r]);
-        }
-        if (j == 0) {
-          (pass ? mean2 : mean1)[row0 + r] = mean;
-          (pass ? rstd2 : rstd1)[row0 + r] = rstd;
-        }
-      }
-    }
-  }
+  geo.fold(pg);
+  geo.fold(pb);
+  ln_write_partials(geo, red, pg, pb, ws, blockIdx.x);
 }
 
 // Backward of the pair.  dz: gradient of z; dres: the gradient reaching y down the residual path (nullable).
 //   xh = (x - m1) r1, y = xh g1 + b1, yh = (y - m2) r2, gz = dz g2
 //   dy = dres + r2 (gz - mean(gz) - yh mean(gz yh)),  gy = dy g1,  dx = r1 (gy - mean(gy) - xh mean(gy xh))
-// Column partials: [dg1 | db1] = [dy xh | dy] in the first nb x 2D block of ws, [dg2 | db2] = [dz yh | dz] in the second
-// (each block laid out as ln_bwd_vec's, so each is one task of the grouped column reduction).  The next row's dz and x
-// loads are issued before this row's reductions: the two dependent reduction stages would otherwise leave a wave with
-// nothing in flight for twice as long as ln_bwd_vec does.
-template <int V, typename TDZ>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void ln_bwd_pair_vec(const TDZ* __restrict__ dz, const float* __restrict__ dres,
-                                                       const float* __restrict__ x, const float* __restrict__ gamma1,
-                                                       const float* __restrict__ beta1,
-                                                       const float* __restrict__ mean1,
-                                                       const float* __restrict__ rstd1,
-                                                       const float* __restrict__ gamma2,
-                                                       const float* __restrict__ mean2,
-                                                       const float* __restrict__ rstd2, float* __restrict__ dx,
-                                                       float* __restrict__ ws, long M, LnDrop dr) {
+// i.e. ln_bwd_stage twice per row, written out (see "shared row code").  Column partials: [dg1 | db1] = [dy xh | dy] in
+// the first nb x 2D block of ws, [dg2 | db2] = [dz yh | dz] in the second (each block laid out as ln_write_partials
+// does, so each is one task of the grouped column reduction; one LDS block serves both in turn).  The next row's dz and x loads are issued before this row's
+// reductions: the two dependent reduction stages would otherwise leave a wave with nothing in flight for twice as
+// long as ln_bwd_wave does.
+template <typename Geom, typename TDZ>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void ln_bwd_pair_wave(
+    const TDZ* __restrict__ dz, const float* __restrict__ dres, const float* __restrict__ x,
+    const float* __restrict__ gamma1, const float* __restrict__ beta1, const float* __restrict__ mean1,
+    const float* __restrict__ rstd1, const float* __restrict__ gamma2, const float* __restrict__ mean2,
+    const float* __restrict__ rstd2, float* __restrict__ dx, float* __restrict__ ws, long M, LnDrop dr) {
+  static_assert(Geom::kWave, "one row per wave");
   if (dr.g2 && dr.p > 0.f) dr.seed = salted_seed(dr.seed, dr.salt);
-  constexpr int D = 64 * V;
-  __shared__ float red[4][2 * D];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  constexpr int F = Geom::F;
+  __shared__ float red[4][2 * Geom::LDSW];
+  const Geom geo(threadIdx.x & 63, 0);
+  const int D = geo.D(), c = geo.col();
+  const int wv = threadIdx.x >> 6;
   const int wglob = blockIdx.x * 4 + wv;
   const int nwaves = gridDim.x * 4;
-  float ga[V], ba[V], gb[V], pg1[V], pb1[V], pg2[V], pb2[V];
-  ldv<V>(gamma1 + lane * V, ga);
-  ldv<V>(beta1 + lane * V, ba);
-  ldv<V>(gamma2 + lane * V, gb);
+  float ga[F], ba[F], gb[F], pg1[F], pb1[F], pg2[F], pb2[F];
+  ldv<F>(gamma1 + c, ga);
+  ldv<F>(beta1 + c, ba);
+  ldv<F>(gamma2 + c, gb);
 #pragma unroll
-  for (int i = 0; i < V; ++i) pg1[i] = pb1[i] = pg2[i] = pb2[i] = 0.f;
-  float d[V], xh[V], st[4];
-  auto fetch = [&](long row, float (&fd)[V], float (&fx)[V], float (&fs)[4]) {
+  for (int i = 0; i < F; ++i) pg1[i] = pb1[i] = pg2[i] = pb2[i] = 0.f;
+  float d[F], xh[F], st[4];
+  auto fetch = [&](long row, float (&fd)[F], float (&fx)[F], float (&fs)[4]) {
     fs[0] = mean1[row]; fs[1] = rstd1[row]; fs[2] = mean2[row]; fs[3] = rstd2[row];
-    ldv<V>(dz + row * D + lane * V, fd);
-    ldv<V>(x + row * D + lane * V, fx);
+    ldv<F>(dz + row * D + c, fd);
+    ldv<F>(x + row * D + c, fx);
   };
   long row = wglob;
   if (row < M) fetch(row, d, xh, st);
   while (row < M) {
     const long nrow = row + nwaves;
-    float o[V], nd[V], nx[V], nst[4];
-    if (dres) ldv<V>(dres + row * D + lane * V, o);   // (needed after the first reduction stage)
+    float o[F], nd[F], nx[F], nst[4];
+    if (dres) ldv<F>(dres + row * D + c, o);   // (needed after the first reduction stage)
     else {
 #pragma unroll
-      for (int i = 0; i < V; ++i) o[i] = 0.f;
+      for (int i = 0; i < F; ++i) o[i] = 0.f;
     }
     if (nrow < M) fetch(nrow, nd, nx, nst);
     const float m1 = st[0], r1 = st[1], m2 = st[2], r2 = st[3];
-    float yh[V], gz[V];
+    float yh[F], gz[F];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-    for (int i = 0; i < V; ++i) {
+    for (int i = 0; i < F; ++i) {
       xh[i] = (xh[i] - m1) * r1;
       yh[i] = (xh[i] * ga[i] + ba[i] - m2) * r2;
       gz[i] = d[i] * gb[i];
@@ -622,11 +578,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
       s1 += gz[i];
       s2 += gz[i] * yh[i];
     }
-    s1 = wave_sum(s1) * (1.f / D);
-    s2 = wave_sum(s2) * (1.f / D);
+    s1 = geo.sum(s1) * geo.inv_d();
+    s2 = geo.sum(s2) * geo.inv_d();
     float t1 = 0.f, t2 = 0.f;
 #pragma unroll
-    for (int i = 0; i < V; ++i) {
+    for (int i = 0; i < F; ++i) {
       o[i] += r2 * (gz[i] - s1 - yh[i] * s2);    // dy
       gz[i] = o[i] * ga[i];                      // gy
       pg1[i] += o[i] * xh[i];
@@ -634,26 +590,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
       t1 += gz[i];
       t2 += gz[i] * xh[i];
     }
-    t1 = wave_sum(t1) * (1.f / D);
-    t2 = wave_sum(t2) * (1.f / D);
+    t1 = geo.sum(t1) * geo.inv_d();
+    t2 = geo.sum(t2) * geo.inv_d();
 #pragma unroll
-    for (int i = 0; i < V; ++i) o[i] = r1 * (gz[i] - t1 - xh[i] * t2);
-    stv<V>(dx + row * D + lane * V, o);
-    if constexpr (V == 8) {
-      if (dr.g2) {   // the module below's input gradient: bf16(dx * scale * dropout mask), as ln_bwd_vec
-        float sc[8];
-        if (dr.p > 0.f) dropout_scale8(dr.p, dr.seed, (uint64_t)(row * D + lane * V), sc);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) sc[i] = dr.p > 0.f ? dr.scale * sc[i] : dr.scale;
-        float q[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) q[i] = o[i] * sc[i];
-        st8_dyn(dr.g2, CFM_BF16, row * D + lane * V, q);
-      }
-    }
+    for (int i = 0; i < F; ++i) o[i] = r1 * (gz[i] - t1 - xh[i] * t2);
+    stv<F>(dx + row * D + c, o);
+    ln_store_g2<Geom>(dr, row * D + c, o);
     if (nrow < M) {
 #pragma unroll
-      for (int i = 0; i < V; ++i) {
+      for (int i = 0; i < F; ++i) {
         d[i] = nd[i];
         xh[i] = nx[i];
       }
@@ -667,33 +612,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
   for (int blk = 0; blk < 2; ++blk) {
     if (blk) __syncthreads();
 #pragma unroll
-    for (int i = 0; i < V; ++i) {
-      red[wv][lane * V + i] = blk ? pg2[i] : pg1[i];
-      red[wv][D + lane * V + i] = blk ? pb2[i] : pb1[i];
+    for (int i = 0; i < F; ++i) {
+      red[wv][c + i] = blk ? pg2[i] : pg1[i];
+      red[wv][D + c + i] = blk ? pb2[i] : pb1[i];
     }
     __syncthreads();
-    for (int c = threadIdx.x; c < 2 * D; c += 256)
-      ws[((long)blk * gridDim.x + blockIdx.x) * 2 * D + c] = red[0][c] + red[1][c] + red[2][c] + red[3][c];
+    for (int q = threadIdx.x; q < 2 * D; q += 256)
+      ws[((long)blk * gridDim.x + blockIdx.x) * 2 * D + q] = red[0][q] + red[1][q] + red[2][q] + red[3][q];
   }
 }
 
-template <int G, typename TDZ>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void ln_bwd_pair_grp(const TDZ* __restrict__ dz, const float* __restrict__ dres,
-                                                       const float* __restrict__ x, const float* __restrict__ gamma1,
-                                                       const float* __restrict__ beta1,
-                                                       const float* __restrict__ mean1,
-                                                       const float* __restrict__ rstd1,
-                                                       const float* __restrict__ gamma2,
-                                                       const float* __restrict__ mean2,
-                                                       const float* __restrict__ rstd2, float* __restrict__ dx,
-                                                       float* __restrict__ ws, long M, int D, LnDrop dr) {
+template <typename Geom, typename TDZ>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void ln_bwd_pair_group(
+    const TDZ* __restrict__ dz, const float* __restrict__ dres, const float* __restrict__ x,
+    const float* __restrict__ gamma1, const float* __restrict__ beta1, const float* __restrict__ mean1,
+    const float* __restrict__ rstd1, const float* __restrict__ gamma2, const float* __restrict__ mean2,
+    const float* __restrict__ rstd2, float* __restrict__ dx, float* __restrict__ ws, long M, int D, LnDrop dr) {
+  static_assert(!Geom::kWave, "a lane group per row");
   if (dr.g2 && dr.p > 0.f) dr.seed = salted_seed(dr.seed, dr.salt);
-  constexpr int RPW = 64 / G;
-  __shared__ float red[4][2 * 8 * G];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane % G, c = 8 * j;
-  const bool act = c < D;
-  const long slot = ((long)blockIdx.x * 4 + wv) * RPW + lane / G;
-  const long nslots = (long)gridDim.x * 4 * RPW;
+  __shared__ float red[4][2 * Geom::LDSW];
+  const Geom geo(threadIdx.x & 63, D);
+  const int c = geo.col();
+  const bool act = geo.act();
+  const int wv = threadIdx.x >> 6;
+  const long slot = ((long)blockIdx.x * 4 + wv) * Geom::RPW + geo.sub();
+  const long nslots = (long)gridDim.x * 4 * Geom::RPW;
   float ga[8], ba[8], gb[8], pg1[8], pb1[8], pg2[8], pb2[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) ga[i] = ba[i] = gb[i] = pg1[i] = pb1[i] = pg2[i] = pb2[i] = 0.f;
@@ -702,10 +645,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
     ldv<8>(beta1 + c, ba);
     ldv<8>(gamma2 + c, gb);
   }
-  const float invd = 1.f / (float)D;
-  // as ln_bwd_grp: the same trip count for every group of the wave (the shuffles span it), rows past M masked.  U
-  // rows per group and iteration: with the four partial rows and three parameter rows a lane holds here, two rows in
-  // flight (ln_bwd_grp's form) do not fit the registers that three waves per SIMD leave
+  // U rows per group and iteration: with the four partial rows and three parameter rows a lane holds here, two rows
+  // in flight (ln_bwd_group's form) do not fit the registers that three waves per SIMD leave
   constexpr int U = 1;
   const long nrow_iter = (M + nslots - 1) / nslots;
   for (long it = 0; it < nrow_iter; it += U) {
@@ -747,8 +688,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
         s1 += gz[i];
         s2 += gz[i] * yh[i];
       }
-      s1 = group_sum<G>(s1) * invd;
-      s2 = group_sum<G>(s2) * invd;
+      s1 = geo.sum(s1) * geo.inv_d();
+      s2 = geo.sum(s2) * geo.inv_d();
       float t1 = 0.f, t2 = 0.f;
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
@@ -759,13 +700,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
         t1 += gz[i];
         t2 += gz[i] * xh[u][i];
       }
-      t1 = group_sum<G>(t1) * invd;
-      t2 = group_sum<G>(t2) * invd;
+      t1 = geo.sum(t1) * geo.inv_d();
+      t2 = geo.sum(t2) * geo.inv_d();
       if (live[u]) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) o[i] = r1[u] * (gz[i] - t1 - xh[u][i] * t2);
         stv<8>(dx + row[u] * D + c, o);
-        if (dr.g2) {
+        if (dr.g2) {   // ln_store_g2, written out: through the function this kernel at G = 64 ran 8 % longer
           float sc[8];
           if (dr.p > 0.f) dropout_scale8(dr.p, dr.seed, (uint64_t)(row[u] * D + c), sc);
 #pragma unroll
@@ -778,30 +719,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void l
       }
     }
   }
-  // fold the groups of the wave (they hold the same columns), then group 0 writes; one LDS block, both pairs in turn
-#pragma unroll
-  for (int o = G; o < 64; o <<= 1) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      pg1[i] += __shfl_xor(pg1[i], o, 64);
-      pb1[i] += __shfl_xor(pb1[i], o, 64);
-      pg2[i] += __shfl_xor(pg2[i], o, 64);
-      pb2[i] += __shfl_xor(pb2[i], o, 64);
-    }
-  }
+  geo.fold(pg1);
+  geo.fold(pb1);
+  geo.fold(pg2);
+  geo.fold(pb2);
+  // one LDS block serves both partial pairs in turn
 #pragma unroll
   for (int blk = 0; blk < 2; ++blk) {
     if (blk) __syncthreads();
-    if (lane < G) {
+    if (geo.heads()) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         red[wv][c + i] = blk ? pg2[i] : pg1[i];
-        red[wv][8 * G + c + i] = blk ? pb2[i] : pb1[i];
+        red[wv][Geom::LDSW + c + i] = blk ? pb2[i] : pb1[i];
       }
     }
     __syncthreads();
     for (int q = threadIdx.x; q < 2 * D; q += 256) {
-      const int k = q < D ? q : 8 * G + (q - D);
+      const int k = q < D ? q : Geom::LDSW + (q - D);
       ws[((long)blk * gridDim.x + blockIdx.x) * 2 * D + q] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
     }
   }
@@ -910,199 +845,116 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
     ws[(long)blockIdx.x * 2 * D + c] = red[0][c] + red[1][c] + red[2][c] + red[3][c];
 }
 
-int ln_bwd_blocks(long M) {
-  long b = (M + 15) / 16;     // ~4 rows per wave
-  return (int)(b < 1024 ? (b < 1 ? 1 : b) : 1024);
-}
+// ---------------------------------------------------------------- host: one dispatcher
+template <typename T> struct LnTag { typedef T type; };
 
-bool aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; }
-
-template <int V>
-bool ln_fwd_fast(const void* x, int dtx, const float* gamma, const float* beta, void* y, int dty, float* mean,
-                 float* rstd, long M, int D, float eps, hipStream_t s, LnMx mx = {}, LnRes rs = {}) {
-  // x: the fp32 residual stream, or bf16 (the bf16 mode's residual stream, conformer.py RES_BF16)
-  if (D != 64 * V || (dtx != CFM_F32 && dtx != CFM_BF16) || !aligned16(x) || !aligned16(y) || !aligned16(gamma) ||
-      !aligned16(beta))
-    return false;
-  dim3 g((unsigned)((M + 4 * LN_FWD_ROWS - 1) / (4 * LN_FWD_ROWS)));
-  if (rs.d) {   // fp32 x + bf16 delta (cfm_layernorm_fwd_res)
-    if (dtx != CFM_F32 || !aligned16(rs.d) || !aligned16(rs.xo) || (V < 4 && ((uintptr_t)rs.d & 15)))
-      return false;
-    if (mx.y8) {
-      if constexpr (V >= 4) {
-        if (dty != CFM_BF16) return false;
-        hipLaunchKernelGGL((ln_fwd_vec<V, bf16, true, float, true>), g, dim3(256), 0, s, (const float*)x, gamma, beta,
-                           (bf16*)y, mean, rstd, M, eps, mx, rs);
-        return true;
-      }
-      return false;
+// Turns a cfm_ln_choice and the runtime dtypes into compile-time tags, once: f(LnTag<Geom>, LnTag<TX>, LnTag<TY>)
+// with Geom = RowWave<V> / RowGroup<G>, TX the type of x and TY that of the other streamed operand (y, z, dy or dz).
+// f launches and returns true, or returns false where its kernel set (the ln_*_exists predicates below) has no such
+// kernel -- ln_plan never chooses one, so false is a bug and the entry points report it.  GENERIC is not f's business.
+template <typename Fn> bool ln_dispatch(const cfm_ln_choice& c, int dtx, int dty, Fn&& f) {
+  auto types = [&](auto geo) {
+    auto ty = [&](auto tx) { return dty == CFM_BF16 ? f(geo, tx, LnTag<bf16>{}) : f(geo, tx, LnTag<float>{}); };
+    return dtx == CFM_BF16 ? ty(LnTag<bf16>{}) : ty(LnTag<float>{});
+  };
+  if (c.family == CFM_LN_WAVE) {
+    switch (c.width) {
+      case 2: return types(LnTag<RowWave<2>>{});
+      case 4: return types(LnTag<RowWave<4>>{});
+      case 8: return types(LnTag<RowWave<8>>{});
+      case 16: return types(LnTag<RowWave<16>>{});
     }
-    if (dty == CFM_BF16)
-      hipLaunchKernelGGL((ln_fwd_vec<V, bf16, false, float, true>), g, dim3(256), 0, s, (const float*)x, gamma, beta,
-                         (bf16*)y, mean, rstd, M, eps, LnMx{}, rs);
-    else
-      hipLaunchKernelGGL((ln_fwd_vec<V, float, false, float, true>), g, dim3(256), 0, s, (const float*)x, gamma, beta,
-                         (float*)y, mean, rstd, M, eps, LnMx{}, rs);
-    return true;
+  } else if (c.family == CFM_LN_GROUP) {
+    switch (c.width) {
+      case 16: return types(LnTag<RowGroup<16>>{});
+      case 32: return types(LnTag<RowGroup<32>>{});
+      case 64: return types(LnTag<RowGroup<64>>{});
+    }
   }
-  auto go = [&](auto xt) {
-    typedef decltype(xt) TX;
-    if (mx.y8) {
-      if constexpr (V >= 4) {
-        if (dty != CFM_BF16) return false;
-        hipLaunchKernelGGL((ln_fwd_vec<V, bf16, true, TX>), g, dim3(256), 0, s, (const TX*)x, gamma, beta, (bf16*)y,
-                           mean, rstd, M, eps, mx);
+  return false;
+}
+// the kernels that exist: the MX copy on RowWave V >= 4 with a bf16 y; x + delta on the fp32 stream; pairs on V 4 / 8
+// and the lane groups, fp32 x
+template <typename Geom, typename TY, bool MX, typename TX, bool RS>
+constexpr bool ln_fwd_exists = (!MX || (Geom::kWave && Geom::F >= 4 && std::is_same<TY, bf16>::value)) &&
+                               (!RS || std::is_same<TX, float>::value);
+template <typename Geom, typename TX>
+constexpr bool ln_pair_exists = (!Geom::kWave || Geom::F == 4 || Geom::F == 8) && std::is_same<TX, float>::value;
+
+#define LN_TAGS(geo, tx, ty)                 \
+  typedef typename decltype(geo)::type Geom; \
+  typedef typename decltype(tx)::type TX;    \
+  typedef typename decltype(ty)::type TY
+
+// The forward of cfm_layernorm_fwd / _fwd_mx_ex / _fwd_res: fills the rest of q, plans, launches.  delta / xout (x +
+// delta) and y8 / s8 (the MX copy) are nullable.
+int ln_forward(const char* who, cfm_ln_query& q, const void* x, int dtx, const void* delta, int dtd, float* xout,
+               const float* gamma, const float* beta, void* y, int dty, void* y8, uint8_t* s8, float* mean, float* rstd,
+               long M, int D, float eps, void* stream) {
+  q.M = M; q.D = D; q.dt_x = dtx; q.dt_y = dty; q.dt_delta = dtd; q.want_mx = y8 != nullptr;
+  q.x_mod16 = ln_mod16(x); q.y_mod16 = ln_mod16(y); q.gamma_mod16 = ln_mod16(gamma); q.beta_mod16 = ln_mod16(beta);
+  q.delta_mod16 = ln_mod16(delta); q.xout_mod16 = ln_mod16(xout); q.y8_mod16 = ln_mod16(y8);
+  cfm_ln_choice c;
+  const int rc = ln_plan(q, c, who);
+  if (rc != CFM_OK || M == 0) return rc;
+  hipStream_t s = cfm::as_stream(stream);
+  if (c.family == CFM_LN_GENERIC) {
+    hipLaunchKernelGGL(ln_fwd_kernel, dim3(c.blocks), dim3(256), 0, s, x, dtx, gamma, beta, y, dty, mean, rstd, M, D,
+                       eps, delta, dtd, xout);
+    return cfm::check_launch(who);
+  }
+  const LnMx mx{(uint8_t*)y8, s8};
+  const LnRes rs{(const bf16*)delta, xout};
+  auto launch = [&](auto mxt, auto rst) {
+    constexpr bool MX = decltype(mxt)::value, RS = decltype(rst)::value;
+    return ln_dispatch(c, dtx, dty, [&](auto geo, auto tx, auto ty) {
+      LN_TAGS(geo, tx, ty);
+      if constexpr (ln_fwd_exists<Geom, TY, MX, TX, RS>) {
+        hipLaunchKernelGGL((ln_fwd<Geom, TY, MX, TX, RS>), dim3(c.blocks), dim3(256), 0, s, (const TX*)x, gamma, beta,
+                           (TY*)y, mean, rstd, M, D, eps, mx, rs);
         return true;
+      } else {
+        return false;
       }
-      return false;
-    }
-    if (dty == CFM_BF16)
-      hipLaunchKernelGGL((ln_fwd_vec<V, bf16, false, TX>), g, dim3(256), 0, s, (const TX*)x, gamma, beta, (bf16*)y, mean,
-                         rstd, M, eps, LnMx{});
-    else
-      hipLaunchKernelGGL((ln_fwd_vec<V, float, false, TX>), g, dim3(256), 0, s, (const TX*)x, gamma, beta, (float*)y,
-                         mean, rstd, M, eps, LnMx{});
-    return true;
+    });
   };
-  return dtx == CFM_BF16 ? go(bf16{}) : go(float{});
+  const std::true_type yes;
+  const std::false_type no;
+  const bool ok = y8 ? (delta ? launch(yes, yes) : launch(yes, no)) : (delta ? launch(no, yes) : launch(no, no));
+  if (!ok) return cfm::fail(CFM_ERR_UNSUPPORTED, std::string(who) + ": no kernel for the plan's choice");
+  return cfm::check_launch(who);
 }
 
-template <int V>
-bool ln_bwd_fast(const void* dy, int dtdy, const void* x, int dtx, const float* gamma, const float* mean,
-                 const float* rstd, const void* dres, int dtres, void* dx, int dtdx, float* ws, long M, int D, int nb,
-                 hipStream_t s, LnDrop dr) {
-  if (D != 64 * V || (dtx != CFM_F32 && dtx != CFM_BF16) || dtdx != CFM_F32 || (dres && dtres != CFM_F32))
-    return false;
-  if (!aligned16(dy) || !aligned16(x) || !aligned16(dres) || !aligned16(dx) || !aligned16(gamma)) return false;
-  if (dr.g2 && (V != 8 || !aligned16(dr.g2))) return false;
-  auto go = [&](auto xt) {
-    typedef decltype(xt) TX;
-    if (dtdy == CFM_BF16)
-      hipLaunchKernelGGL((ln_bwd_vec<V, bf16, TX>), dim3(nb), dim3(256), 0, s, (const bf16*)dy, (const TX*)x, gamma,
-                         mean, rstd, (const float*)dres, (float*)dx, ws, M, dr);
-    else
-      hipLaunchKernelGGL((ln_bwd_vec<V, float, TX>), dim3(nb), dim3(256), 0, s, (const float*)dy, (const TX*)x, gamma,
-                         mean, rstd, (const float*)dres, (float*)dx, ws, M, dr);
-  };
-  if (dtx == CFM_BF16) go(bf16{});
-  else go(float{});
-  return true;
-}
-// D % 8 == 0 widths below 512 that are not 64 * V: the lane-group kernels (G = next power of two >= D / 8)
-int ln_group(int D) {
-  if (D % 8 || D > 512) return 0;
-  const int n = D / 8;
-  return n <= 16 ? 16 : n <= 32 ? 32 : 64;
-}
-
-bool ln_fwd_grouped(const void* x, int dtx, const float* gamma, const float* beta, void* y, int dty, float* mean,
-                    float* rstd, long M, int D, float eps, hipStream_t s, LnRes rs = {}) {
-  const int G = ln_group(D);
-  if (!G || (dtx != CFM_F32 && dtx != CFM_BF16) || (dty != CFM_F32 && dty != CFM_BF16) || !aligned16(x) ||
-      !aligned16(y) || !aligned16(gamma) || !aligned16(beta))
-    return false;
-  if (rs.d && (dtx != CFM_F32 || !aligned16(rs.d) || !aligned16(rs.xo))) return false;
-  const long rows_per_block = 4L * (64 / G) * LN_FWD_ROWS;
-  const dim3 g((unsigned)((M + rows_per_block - 1) / rows_per_block));
-  auto go = [&](auto gt) {
-    constexpr int GG = decltype(gt)::value;
-    if (rs.d) {
-      if (dty == CFM_BF16)
-        hipLaunchKernelGGL((ln_fwd_grp<GG, bf16, float, true>), g, dim3(256), 0, s, (const float*)x, gamma, beta,
-                           (bf16*)y, mean, rstd, M, D, eps, rs);
-      else
-        hipLaunchKernelGGL((ln_fwd_grp<GG, float, float, true>), g, dim3(256), 0, s, (const float*)x, gamma, beta,
-                           (float*)y, mean, rstd, M, D, eps, rs);
-      return;
-    }
-    auto go2 = [&](auto xt) {
-      typedef decltype(xt) TX;
-      if (dty == CFM_BF16)
-        hipLaunchKernelGGL((ln_fwd_grp<GG, bf16, TX>), g, dim3(256), 0, s, (const TX*)x, gamma, beta, (bf16*)y, mean,
-                           rstd, M, D, eps);
-      else
-        hipLaunchKernelGGL((ln_fwd_grp<GG, float, TX>), g, dim3(256), 0, s, (const TX*)x, gamma, beta, (float*)y,
-                           mean, rstd, M, D, eps);
-    };
-    if (dtx == CFM_BF16) go2(bf16{});
-    else go2(float{});
-  };
-  if (G == 16) go(std::integral_constant<int, 16>{});
-  else if (G == 32) go(std::integral_constant<int, 32>{});
-  else go(std::integral_constant<int, 64>{});
-  return true;
-}
-
-bool ln_bwd_grouped(const void* dy, int dtdy, const void* x, int dtx, const float* gamma, const float* mean,
-                    const float* rstd, const void* dres, int dtres, void* dx, int dtdx, float* ws, long M, int D,
-                    int nb, hipStream_t s, LnDrop dr) {
-  const int G = ln_group(D);
-  if (!G || (dtx != CFM_F32 && dtx != CFM_BF16) || dtdx != CFM_F32 || (dres && dtres != CFM_F32)) return false;
-  if (dtdy != CFM_BF16 && dtdy != CFM_F32) return false;
-  if (!aligned16(dy) || !aligned16(x) || !aligned16(dres) || !aligned16(dx) || !aligned16(gamma)) return false;
-  if (dr.g2 && !aligned16(dr.g2)) return false;
-  auto go = [&](auto gt) {
-    constexpr int GG = decltype(gt)::value;
-    auto go2 = [&](auto xt) {
-      typedef decltype(xt) TX;
-      if (dtdy == CFM_BF16)
-        hipLaunchKernelGGL((ln_bwd_grp<GG, bf16, TX>), dim3(nb), dim3(256), 0, s, (const bf16*)dy, (const TX*)x, gamma,
-                           mean, rstd, (const float*)dres, (float*)dx, ws, M, D, dr);
-      else
-        hipLaunchKernelGGL((ln_bwd_grp<GG, float, TX>), dim3(nb), dim3(256), 0, s, (const float*)dy, (const TX*)x,
-                           gamma, mean, rstd, (const float*)dres, (float*)dx, ws, M, D, dr);
-    };
-    if (dtx == CFM_BF16) go2(bf16{});
-    else go2(float{});
-  };
-  if (G == 16) go(std::integral_constant<int, 16>{});
-  else if (G == 32) go(std::integral_constant<int, 32>{});
-  else go(std::integral_constant<int, 64>{});
-  return true;
-}
-// which fused pair kernels serve width D with z / dz of dtype dtz: 0 none, 8 / 4 the one-row-per-wave kernels at that
-// V (D 512 / 256), -G the lane-group kernels.  D 128 and 1024 run ln_*_vec<2> / <16> in the two-call path and have no
-// fused form.  Pure host logic (cfm_layernorm_pair_ok).
-int ln_pair_kind(int D, int dtz) {
-  if (dtz != CFM_F32 && dtz != CFM_BF16) return 0;
-  if (D == 512) return 8;
-  if (D == 256) return 4;
-  if (D <= 0 || D == 128) return 0;
-  return -ln_group(D);
+// the column reductions behind a backward kernel: out (+)= the nb partial rows of ws
+void ln_reduce_cols(float* ws, int nb, int D, float* dgamma, float* dbeta, hipStream_t s) {
+  if (dgamma && dbeta && dbeta == dgamma + D) {
+    cfm::colreduce(ws, nb, 2L * D, dgamma, 0, s);               // one pass for [dgamma | dbeta]
+  } else {
+    if (dgamma) cfm::colreduce(ws, nb, D, dgamma, 0, s, 2L * D);
+    if (dbeta) cfm::colreduce(ws + D, nb, D, dbeta, 0, s, 2L * D);
+  }
 }
 }  // namespace
+
+CFM_EXPORT int cfm_layernorm_plan(const cfm_ln_query* q, cfm_ln_choice* out) {
+  CFM_REQUIRE(q && out, CFM_ERR_ARG, "null pointer");
+  return ln_plan(*q, *out, "cfm_layernorm_plan");
+}
 
 CFM_EXPORT int cfm_layernorm_fwd(const void* x, int dtx, const float* gamma, const float* beta, void* y, int dty,
                                  float* mean, float* rstd, long M, int D, float eps, void* stream) {
   CFM_REQUIRE(x && gamma && beta && y && mean && rstd, CFM_ERR_ARG, "null pointer");
-  CFM_REQUIRE(D > 0 && D <= 64 * MAXJ && M >= 0, CFM_ERR_SHAPE, "D must be in (0, 1024]");
-  if (M == 0) return CFM_OK;
-  hipStream_t s = cfm::as_stream(stream);
-  const bool fast = ln_fwd_fast<2>(x, dtx, gamma, beta, y, dty, mean, rstd, M, D, eps, s) ||
-                    ln_fwd_fast<4>(x, dtx, gamma, beta, y, dty, mean, rstd, M, D, eps, s) ||
-                    ln_fwd_fast<8>(x, dtx, gamma, beta, y, dty, mean, rstd, M, D, eps, s) ||
-                    ln_fwd_fast<16>(x, dtx, gamma, beta, y, dty, mean, rstd, M, D, eps, s) ||
-                    ln_fwd_grouped(x, dtx, gamma, beta, y, dty, mean, rstd, M, D, eps, s);
-  if (!fast)
-    hipLaunchKernelGGL(ln_fwd_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, x, dtx, gamma, beta, y, dty,
-                       mean, rstd, M, D, eps);
-  return cfm::check_launch("cfm_layernorm_fwd");
+  cfm_ln_query q{CFM_LN_FWD};
+  return ln_forward("cfm_layernorm_fwd", q, x, dtx, nullptr, 0, nullptr, gamma, beta, y, dty, nullptr, nullptr, mean,
+                    rstd, M, D, eps, stream);
 }
 
 CFM_EXPORT int cfm_layernorm_fwd_mx_ex(const void* x, int dtx, const float* gamma, const float* beta, void* y, void* y8,
                                        uint8_t* s8, float* mean, float* rstd, long M, int D, float eps, void* stream) {
   CFM_REQUIRE(x && gamma && beta && y && y8 && s8 && mean && rstd, CFM_ERR_ARG, "null pointer");
-  CFM_REQUIRE(dtx == CFM_F32 || dtx == CFM_BF16, CFM_ERR_DTYPE, "x: f32 or bf16");
-  CFM_REQUIRE((D == 256 || D == 512 || D == 1024) && M >= 0, CFM_ERR_SHAPE, "D in {256, 512, 1024}");
-  CFM_REQUIRE((uintptr_t)y8 % 8 == 0, CFM_ERR_ALIGN, "8-B aligned y8");
-  if (M == 0) return CFM_OK;
-  hipStream_t s = cfm::as_stream(stream);
-  const LnMx mx{(uint8_t*)y8, s8};
-  const bool ok = ln_fwd_fast<4>(x, dtx, gamma, beta, y, CFM_BF16, mean, rstd, M, D, eps, s, mx) ||
-                  ln_fwd_fast<8>(x, dtx, gamma, beta, y, CFM_BF16, mean, rstd, M, D, eps, s, mx) ||
-                  ln_fwd_fast<16>(x, dtx, gamma, beta, y, CFM_BF16, mean, rstd, M, D, eps, s, mx);
-  CFM_REQUIRE(ok, CFM_ERR_ALIGN, "16-B aligned x / y / gamma / beta");
-  return cfm::check_launch("cfm_layernorm_fwd_mx");
+  cfm_ln_query q{CFM_LN_FWD};
+  return ln_forward("cfm_layernorm_fwd_mx", q, x, dtx, nullptr, 0, nullptr, gamma, beta, y, CFM_BF16, y8, s8, mean,
+                    rstd, M, D, eps, stream);
 }
 
 CFM_EXPORT int cfm_layernorm_fwd_res(const float* x, const void* delta, int dtd, float* xout, const float* gamma,
@@ -1111,29 +963,10 @@ CFM_EXPORT int cfm_layernorm_fwd_res(const float* x, const void* delta, int dtd,
   CFM_REQUIRE(x && delta && xout && gamma && beta && y && mean && rstd, CFM_ERR_ARG, "null pointer");
   CFM_REQUIRE((const void*)x != (const void*)xout && delta != (const void*)xout, CFM_ERR_ARG,
               "xout must not alias x or delta");
-  CFM_REQUIRE(dtd == CFM_F32 || dtd == CFM_BF16, CFM_ERR_DTYPE, "delta: f32 or bf16");
-  CFM_REQUIRE(dty == CFM_F32 || dty == CFM_BF16, CFM_ERR_DTYPE, "y: f32 or bf16");
-  CFM_REQUIRE(D > 0 && D <= 64 * MAXJ && M >= 0, CFM_ERR_SHAPE, "D must be in (0, 1024]");
-  CFM_REQUIRE(!y8 || (s8 && dty == CFM_BF16 && (D == 256 || D == 512 || D == 1024) && (uintptr_t)y8 % 8 == 0),
-              CFM_ERR_SHAPE, "MX copy: bf16 y, D in {256, 512, 1024}, 8-B aligned y8, s8");
-  if (M == 0) return CFM_OK;
-  hipStream_t s = cfm::as_stream(stream);
-  const LnMx mx{(uint8_t*)y8, s8};
-  const LnRes rs{dtd == CFM_BF16 ? (const bf16*)delta : nullptr, xout};
-  bool fast = false;
-  if (rs.d) {
-    fast = ln_fwd_fast<2>(x, CFM_F32, gamma, beta, y, dty, mean, rstd, M, D, eps, s, mx, rs) ||
-           ln_fwd_fast<4>(x, CFM_F32, gamma, beta, y, dty, mean, rstd, M, D, eps, s, mx, rs) ||
-           ln_fwd_fast<8>(x, CFM_F32, gamma, beta, y, dty, mean, rstd, M, D, eps, s, mx, rs) ||
-           ln_fwd_fast<16>(x, CFM_F32, gamma, beta, y, dty, mean, rstd, M, D, eps, s, mx, rs) ||
-           (!y8 && ln_fwd_grouped(x, CFM_F32, gamma, beta, y, dty, mean, rstd, M, D, eps, s, rs));
-  }
-  if (!fast) {
-    CFM_REQUIRE(!y8, CFM_ERR_ALIGN, "MX copy: 16-B aligned x / delta / xout / y / gamma / beta");
-    hipLaunchKernelGGL(ln_fwd_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, (const void*)x, (int)CFM_F32,
-                       gamma, beta, y, dty, mean, rstd, M, D, eps, delta, dtd, xout);
-  }
-  return cfm::check_launch("cfm_layernorm_fwd_res");
+  CFM_REQUIRE(!y8 || s8, CFM_ERR_SHAPE, "MX copy: y8 and s8");
+  cfm_ln_query q{CFM_LN_FWD_RES};
+  return ln_forward("cfm_layernorm_fwd_res", q, x, CFM_F32, delta, dtd, xout, gamma, beta, y, dty, y8, s8, mean, rstd,
+                    M, D, eps, stream);
 }
 
 CFM_EXPORT int cfm_layernorm_fwd_mx(const float* x, const float* gamma, const float* beta, void* y, void* y8,
@@ -1141,8 +974,11 @@ CFM_EXPORT int cfm_layernorm_fwd_mx(const float* x, const float* gamma, const fl
   return cfm_layernorm_fwd_mx_ex(x, CFM_F32, gamma, beta, y, y8, s8, mean, rstd, M, D, eps, stream);
 }
 
+// the workspace of a backward over M rows of width D; 0 where the entry point refuses the shape
 CFM_EXPORT size_t cfm_layernorm_ws_bytes(long M, int D) {
-  return (size_t)ln_bwd_blocks(M) * 2 * D * sizeof(float) + 2 * D * sizeof(float);
+  cfm_ln_query q{CFM_LN_BWD, D, M};
+  cfm_ln_choice c;
+  return ln_plan(q, c, "cfm_layernorm_ws_bytes") == CFM_OK ? c.ws_bytes : 0;
 }
 
 CFM_EXPORT int cfm_scale_dropout(const void* x, int dtx, void* y, int dty, long n, float scale, float p,
@@ -1153,37 +989,35 @@ CFM_EXPORT int cfm_layernorm_bwd_drop(const void* dy, int dtdy, const void* x, i
                                       int dtdx, float* dgamma, float* dbeta, float* ws, long M, int D, void* g2,
                                       float g2_scale, float g2_p, uint64_t g2_seed, void* stream) {
   CFM_REQUIRE(dy && x && gamma && mean && rstd && dx && ws, CFM_ERR_ARG, "null pointer");
-  CFM_REQUIRE(D > 0 && D <= 64 * MAXJ && M >= 0, CFM_ERR_SHAPE, "D must be in (0, 1024]");
+  cfm_ln_query q{CFM_LN_BWD, D, M};
+  q.dt_x = dtx; q.dt_dy = dtdy; q.dt_dx = dtdx; q.dt_dres = dres ? dtres : (int)CFM_F32; q.want_g2 = g2 != nullptr;
+  q.dy_mod16 = ln_mod16(dy); q.x_mod16 = ln_mod16(x); q.gamma_mod16 = ln_mod16(gamma); q.dres_mod16 = ln_mod16(dres);
+  q.dx_mod16 = ln_mod16(dx); q.g2_mod16 = ln_mod16(g2);
+  cfm_ln_choice c;
+  const int rc = ln_plan(q, c, "cfm_layernorm_bwd");
+  if (rc != CFM_OK) return rc;
   hipStream_t s = cfm::as_stream(stream);
-  const int nb = ln_bwd_blocks(M);
-  const LnDrop dr{g2, g2_scale, g2_p, g2_seed, cfm::g_rng_salt};
-  bool fast = ln_bwd_fast<2>(dy, dtdy, x, dtx, gamma, mean, rstd, dres, dtres, dx, dtdx, ws, M, D, nb, s, dr) ||
-              ln_bwd_fast<4>(dy, dtdy, x, dtx, gamma, mean, rstd, dres, dtres, dx, dtdx, ws, M, D, nb, s, dr) ||
-              ln_bwd_fast<8>(dy, dtdy, x, dtx, gamma, mean, rstd, dres, dtres, dx, dtdx, ws, M, D, nb, s, dr) ||
-              ln_bwd_fast<16>(dy, dtdy, x, dtx, gamma, mean, rstd, dres, dtres, dx, dtdx, ws, M, D, nb, s, dr) ||
-              ln_bwd_grouped(dy, dtdy, x, dtx, gamma, mean, rstd, dres, dtres, dx, dtdx, ws, M, D, nb, s, dr);
-  bool g2_done = fast && g2 != nullptr;
-  if (!fast && g2) {   // no fused path for this shape: the vectorised kernel without g2, then a separate pass
-    const LnDrop none{nullptr, 0.f, 0.f, 0, nullptr};
-    fast = ln_bwd_fast<2>(dy, dtdy, x, dtx, gamma, mean, rstd, dres, dtres, dx, dtdx, ws, M, D, nb, s, none) ||
-           ln_bwd_fast<4>(dy, dtdy, x, dtx, gamma, mean, rstd, dres, dtres, dx, dtdx, ws, M, D, nb, s, none) ||
-           ln_bwd_fast<8>(dy, dtdy, x, dtx, gamma, mean, rstd, dres, dtres, dx, dtdx, ws, M, D, nb, s, none) ||
-           ln_bwd_fast<16>(dy, dtdy, x, dtx, gamma, mean, rstd, dres, dtres, dx, dtdx, ws, M, D, nb, s, none) ||
-           ln_bwd_grouped(dy, dtdy, x, dtx, gamma, mean, rstd, dres, dtres, dx, dtdx, ws, M, D, nb, s, none);
-  }
-  if (!fast)
-    hipLaunchKernelGGL(ln_bwd_kernel, dim3(nb), dim3(256), 0, s, dy, dtdy, x, dtx, gamma, mean, rstd, dres, dtres,
+  const LnDrop dr{c.g2_fused ? g2 : nullptr, g2_scale, g2_p, g2_seed, cfm::g_rng_salt};
+  if (c.family == CFM_LN_GENERIC) {
+    hipLaunchKernelGGL(ln_bwd_kernel, dim3(c.blocks), dim3(256), 0, s, dy, dtdy, x, dtx, gamma, mean, rstd, dres, dtres,
                        dx, dtdx, ws, M, D);
-  if (g2 && !g2_done) {
-    const int rc = cfm_scale_dropout(dx, dtdx, g2, CFM_BF16, M * D, g2_scale, g2_p, g2_seed, 0, stream);
-    if (rc != CFM_OK) return rc;
-  }
-  if (dgamma && dbeta && dbeta == dgamma + D) {
-    cfm::colreduce(ws, nb, 2L * D, dgamma, 0, s);               // one pass for [dgamma | dbeta]
   } else {
-    if (dgamma) cfm::colreduce(ws, nb, D, dgamma, 0, s, 2L * D);
-    if (dbeta) cfm::colreduce(ws + D, nb, D, dbeta, 0, s, 2L * D);
+    ln_dispatch(c, dtx, dtdy, [&](auto geo, auto tx, auto ty) {
+      LN_TAGS(geo, tx, ty);
+      if constexpr (Geom::kWave)
+        hipLaunchKernelGGL((ln_bwd_wave<Geom, TY, TX>), dim3(c.blocks), dim3(256), 0, s, (const TY*)dy, (const TX*)x,
+                           gamma, mean, rstd, (const float*)dres, (float*)dx, ws, M, dr);
+      else
+        hipLaunchKernelGGL((ln_bwd_group<Geom, TY, TX>), dim3(c.blocks), dim3(256), 0, s, (const TY*)dy, (const TX*)x,
+                           gamma, mean, rstd, (const float*)dres, (float*)dx, ws, M, D, dr);
+      return true;
+    });
   }
+  if (g2 && !c.g2_fused) {
+    const int rc2 = cfm_scale_dropout(dx, dtdx, g2, CFM_BF16, M * D, g2_scale, g2_p, g2_seed, 0, stream);
+    if (rc2 != CFM_OK) return rc2;
+  }
+  ln_reduce_cols(ws, c.blocks, D, dgamma, dbeta, s);
   return cfm::check_launch("cfm_layernorm_bwd");
 }
 
@@ -1195,7 +1029,12 @@ CFM_EXPORT int cfm_layernorm_bwd(const void* dy, int dtdy, const void* x, int dt
                                 nullptr, 0.f, 0.f, 0, stream);
 }
 
-CFM_EXPORT int cfm_layernorm_pair_ok(int D, int dtype_z) { return ln_pair_kind(D, dtype_z) != 0; }
+CFM_EXPORT int cfm_layernorm_pair_ok(int D, int dtype_z) {
+  cfm_ln_query q{CFM_LN_FWD_PAIR, D, 0};
+  q.dt_y = dtype_z;
+  cfm_ln_choice c;
+  return ln_plan(q, c, "cfm_layernorm_pair_ok") == CFM_OK;
+}
 
 CFM_EXPORT size_t cfm_layernorm_fwd_pair_ws_bytes(long, int) { return 0; }
 
@@ -1204,45 +1043,32 @@ CFM_EXPORT int cfm_layernorm_fwd_pair(const float* x, const float* gamma1, const
                                       float* mean2, float* rstd2, long M, int D, float eps, void* stream) {
   CFM_REQUIRE(x && gamma1 && beta1 && gamma2 && beta2 && y && z && mean1 && rstd1 && mean2 && rstd2, CFM_ERR_ARG,
               "null pointer");
-  CFM_REQUIRE(M >= 0, CFM_ERR_SHAPE, "M >= 0");
-  const int kind = ln_pair_kind(D, dtz);
-  CFM_REQUIRE(kind != 0, CFM_ERR_SHAPE, "no fused pair kernel for this width / dtype (cfm_layernorm_pair_ok)");
-  CFM_REQUIRE(aligned16(x) && aligned16(y) && aligned16(z) && aligned16(gamma1) && aligned16(beta1) &&
-                  aligned16(gamma2) && aligned16(beta2),
-              CFM_ERR_ALIGN, "16-B aligned x / y / z / gamma / beta");
-  if (M == 0) return CFM_OK;
+  cfm_ln_query q{CFM_LN_FWD_PAIR, D, M};
+  q.dt_y = dtz;
+  q.x_mod16 = ln_mod16(x); q.y_mod16 = ln_mod16(y); q.z_mod16 = ln_mod16(z); q.gamma_mod16 = ln_mod16(gamma1);
+  q.beta_mod16 = ln_mod16(beta1); q.gamma2_mod16 = ln_mod16(gamma2); q.beta2_mod16 = ln_mod16(beta2);
+  cfm_ln_choice c;
+  const int rc = ln_plan(q, c, "cfm_layernorm_fwd_pair");
+  if (rc != CFM_OK || M == 0) return rc;
   hipStream_t s = cfm::as_stream(stream);
-  auto vec = [&](auto vt) {
-    constexpr int V = decltype(vt)::value;
-    const dim3 g((unsigned)((M + 4 * LN_FWD_ROWS - 1) / (4 * LN_FWD_ROWS)));
-    if (dtz == CFM_BF16)
-      hipLaunchKernelGGL((ln_fwd_pair_vec<V, bf16>), g, dim3(256), 0, s, x, gamma1, beta1, gamma2, beta2, y, (bf16*)z,
-                         mean1, rstd1, mean2, rstd2, M, eps);
-    else
-      hipLaunchKernelGGL((ln_fwd_pair_vec<V, float>), g, dim3(256), 0, s, x, gamma1, beta1, gamma2, beta2, y,
-                         (float*)z, mean1, rstd1, mean2, rstd2, M, eps);
-  };
-  auto grp = [&](auto gt) {
-    constexpr int G = decltype(gt)::value;
-    const long rows_per_block = 4L * (64 / G) * LN_FWD_ROWS;
-    const dim3 g((unsigned)((M + rows_per_block - 1) / rows_per_block));
-    if (dtz == CFM_BF16)
-      hipLaunchKernelGGL((ln_fwd_pair_grp<G, bf16>), g, dim3(256), 0, s, x, gamma1, beta1, gamma2, beta2, y, (bf16*)z,
-                         mean1, rstd1, mean2, rstd2, M, D, eps);
-    else
-      hipLaunchKernelGGL((ln_fwd_pair_grp<G, float>), g, dim3(256), 0, s, x, gamma1, beta1, gamma2, beta2, y,
-                         (float*)z, mean1, rstd1, mean2, rstd2, M, D, eps);
-  };
-  if (kind == 8) vec(std::integral_constant<int, 8>{});
-  else if (kind == 4) vec(std::integral_constant<int, 4>{});
-  else if (kind == -16) grp(std::integral_constant<int, 16>{});
-  else if (kind == -32) grp(std::integral_constant<int, 32>{});
-  else grp(std::integral_constant<int, 64>{});
+  ln_dispatch(c, CFM_F32, dtz, [&](auto geo, auto tx, auto ty) {
+    LN_TAGS(geo, tx, ty);
+    if constexpr (ln_pair_exists<Geom, TX>) {
+      hipLaunchKernelGGL((ln_fwd_pair<Geom, TY>), dim3(c.blocks), dim3(256), 0, s, x, gamma1, beta1, gamma2, beta2, y,
+                         (TY*)z, mean1, rstd1, mean2, rstd2, M, D, eps);
+      return true;
+    } else {
+      return false;
+    }
+  });
   return cfm::check_launch("cfm_layernorm_fwd_pair");
 }
 
+// 0 where no fused pair kernel exists (cfm_layernorm_pair_ok)
 CFM_EXPORT size_t cfm_layernorm_bwd_pair_ws_bytes(long M, int D) {
-  return (size_t)ln_bwd_blocks(M) * 4 * D * sizeof(float);
+  cfm_ln_query q{CFM_LN_BWD_PAIR, D, M};
+  cfm_ln_choice c;
+  return ln_plan(q, c, "cfm_layernorm_bwd_pair_ws_bytes") == CFM_OK ? c.ws_bytes : 0;
 }
 
 CFM_EXPORT int cfm_layernorm_bwd_pair(const void* dz, int dtdz, const float* dres, const float* x,
@@ -1252,44 +1078,34 @@ CFM_EXPORT int cfm_layernorm_bwd_pair(const void* dz, int dtdz, const float* dre
                                       float g2_p, uint64_t g2_seed, void* stream) {
   CFM_REQUIRE(dz && x && gamma1 && beta1 && mean1 && rstd1 && gamma2 && mean2 && rstd2 && dx && ws, CFM_ERR_ARG,
               "null pointer");
-  CFM_REQUIRE(M >= 0, CFM_ERR_SHAPE, "M >= 0");
-  const int kind = ln_pair_kind(D, dtdz);
-  CFM_REQUIRE(kind != 0, CFM_ERR_SHAPE, "no fused pair kernel for this width / dtype (cfm_layernorm_pair_ok)");
-  CFM_REQUIRE(aligned16(dz) && aligned16(dres) && aligned16(x) && aligned16(dx) && aligned16(gamma1) &&
-                  aligned16(beta1) && aligned16(gamma2) && aligned16(g2),
-              CFM_ERR_ALIGN, "16-B aligned dz / dres / x / dx / gamma / beta / g2");
+  cfm_ln_query q{CFM_LN_BWD_PAIR, D, M};
+  q.dt_dy = dtdz; q.want_g2 = g2 != nullptr;
+  q.dy_mod16 = ln_mod16(dz); q.dres_mod16 = ln_mod16(dres); q.x_mod16 = ln_mod16(x); q.dx_mod16 = ln_mod16(dx);
+  q.gamma_mod16 = ln_mod16(gamma1); q.beta_mod16 = ln_mod16(beta1); q.gamma2_mod16 = ln_mod16(gamma2);
+  q.g2_mod16 = ln_mod16(g2);
+  cfm_ln_choice c;
+  const int rc = ln_plan(q, c, "cfm_layernorm_bwd_pair");
+  if (rc != CFM_OK) return rc;
   hipStream_t s = cfm::as_stream(stream);
-  const int nb = ln_bwd_blocks(M);
-  // g2 from the same pass where ln_bwd_* has it (V = 8 and the lane-group kernels); else a separate pass, as
-  // cfm_layernorm_bwd_drop
-  const bool g2_fused = g2 && kind != 4;
-  const LnDrop dr{g2_fused ? g2 : nullptr, g2_scale, g2_p, g2_seed, cfm::g_rng_salt};
-  auto vec = [&](auto vt) {
-    constexpr int V = decltype(vt)::value;
-    if (dtdz == CFM_BF16)
-      hipLaunchKernelGGL((ln_bwd_pair_vec<V, bf16>), dim3(nb), dim3(256), 0, s, (const bf16*)dz, dres, x, gamma1,
-                         beta1, mean1, rstd1, gamma2, mean2, rstd2, dx, ws, M, dr);
-    else
-      hipLaunchKernelGGL((ln_bwd_pair_vec<V, float>), dim3(nb), dim3(256), 0, s, (const float*)dz, dres, x, gamma1,
-                         beta1, mean1, rstd1, gamma2, mean2, rstd2, dx, ws, M, dr);
-  };
-  auto grp = [&](auto gt) {
-    constexpr int G = decltype(gt)::value;
-    if (dtdz == CFM_BF16)
-      hipLaunchKernelGGL((ln_bwd_pair_grp<G, bf16>), dim3(nb), dim3(256), 0, s, (const bf16*)dz, dres, x, gamma1,
-                         beta1, mean1, rstd1, gamma2, mean2, rstd2, dx, ws, M, D, dr);
-    else
-      hipLaunchKernelGGL((ln_bwd_pair_grp<G, float>), dim3(nb), dim3(256), 0, s, (const float*)dz, dres, x, gamma1,
-                         beta1, mean1, rstd1, gamma2, mean2, rstd2, dx, ws, M, D, dr);
-  };
-  if (kind == 8) vec(std::integral_constant<int, 8>{});
-  else if (kind == 4) vec(std::integral_constant<int, 4>{});
-  else if (kind == -16) grp(std::integral_constant<int, 16>{});
-  else if (kind == -32) grp(std::integral_constant<int, 32>{});
-  else grp(std::integral_constant<int, 64>{});
-  if (g2 && !g2_fused) {
-    const int rc = cfm_scale_dropout(dx, CFM_F32, g2, CFM_BF16, M * D, g2_scale, g2_p, g2_seed, 0, stream);
-    if (rc != CFM_OK) return rc;
+  const int nb = c.blocks;
+  const LnDrop dr{c.g2_fused ? g2 : nullptr, g2_scale, g2_p, g2_seed, cfm::g_rng_salt};
+  ln_dispatch(c, CFM_F32, dtdz, [&](auto geo, auto tx, auto ty) {
+    LN_TAGS(geo, tx, ty);
+    if constexpr (!ln_pair_exists<Geom, TX>) {
+      return false;
+    } else {
+      if constexpr (Geom::kWave)
+        hipLaunchKernelGGL((ln_bwd_pair_wave<Geom, TY>), dim3(nb), dim3(256), 0, s, (const TY*)dz, dres, x, gamma1,
+                           beta1, mean1, rstd1, gamma2, mean2, rstd2, dx, ws, M, dr);
+      else
+        hipLaunchKernelGGL((ln_bwd_pair_group<Geom, TY>), dim3(nb), dim3(256), 0, s, (const TY*)dz, dres, x, gamma1,
+                           beta1, mean1, rstd1, gamma2, mean2, rstd2, dx, ws, M, D, dr);
+      return true;
+    }
+  });
+  if (g2 && !c.g2_fused) {
+    const int rc2 = cfm_scale_dropout(dx, CFM_F32, g2, CFM_BF16, M * D, g2_scale, g2_p, g2_seed, 0, stream);
+    if (rc2 != CFM_OK) return rc2;
   }
   float* part2 = ws + (long)nb * 2 * D;
   if (dgb1 && dgb2) cfm::colreduce_pair(ws, part2, nb, 2L * D, dgb1, dgb2, s);

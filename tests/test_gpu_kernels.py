@@ -198,31 +198,93 @@ def test_gemm_dropout_deterministic():
     assert torch.allclose(o1[kept], ref[kept] / 0.75, rtol=1e-4, atol=1e-4)
 
 
-@pytest.mark.parametrize("D", [144, 256, 512, 100, 64, 200, 384])
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-def test_layernorm(D, dtype):
-    """64 * V widths on the one-row-per-wave kernels, other multiples of 8 (Conformer-S 144, 64, 200, 384) on the
-    lane-group kernels, the rest (100) on the generic strided kernels."""
+def _layernorm_case(D, M):
     g = torch.Generator().manual_seed(D)
-    M = 777
     x = torch.randn(M, D, generator=g) * 2 + 0.3
     gamma = torch.rand(D, generator=g) + 0.5
     beta = torch.randn(D, generator=g)
-    y, mean, rstd = ops.layernorm_fwd(x.to(DEV), gamma.to(DEV), beta.to(DEV), out_dtype=dtype)
     xr = x.clone().requires_grad_()
     gr = gamma.clone().requires_grad_()
     br = beta.clone().requires_grad_()
     yr = torch.nn.functional.layer_norm(xr, (D,), gr, br, 1e-5)
-    assert _rel(y, yr) < (1e-6 if dtype == torch.float32 else 5e-3)
     dy = torch.randn(M, D, generator=g)
     dres = torch.randn(M, D, generator=g)
     yr.backward(dy)
+    return x, gamma, beta, dy, dres, yr.detach(), xr.grad + dres, gr.grad, br.grad
+
+
+def _check_layernorm(D, M, dtype):
+    x, gamma, beta, dy, dres, yr, dxr, dgr, dbr = _layernorm_case(D, M)
+    y, mean, rstd = ops.layernorm_fwd(x.to(DEV), gamma.to(DEV), beta.to(DEV), out_dtype=dtype)
+    assert _rel(y, yr) < (1e-6 if dtype == torch.float32 else 5e-3)
     dx, dgamma, dbeta = ops.layernorm_bwd(dy.to(DEV, dtype), x.to(DEV), gamma.to(DEV), mean, rstd,
                                           dres=dres.to(DEV))
     tol = 1e-5 if dtype == torch.float32 else 1e-2
-    assert _rel(dx, xr.grad + dres) < tol
-    assert _rel(dgamma, gr.grad) < tol
-    assert _rel(dbeta, br.grad) < tol
+    assert _rel(dx, dxr) < tol
+    assert _rel(dgamma, dgr) < tol
+    assert _rel(dbeta, dbr) < tol
+
+
+@pytest.mark.parametrize("D", [144, 256, 512, 100, 64, 200, 384, 128, 1024])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_layernorm(D, dtype):
+    """64 * V widths (128 ... 1024: V = 2, 4, 8, 16) on the one-row-per-wave kernels, other multiples of 8
+    (Conformer-S 144, 64, 200, 384) on the lane-group kernels, the rest (100) on the generic strided kernels."""
+    _check_layernorm(D, 777, dtype)
+
+
+@pytest.mark.parametrize("D,M", [(144, 1), (144, 9), (512, 1), (512, 9)])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_layernorm_partial_wave(D, M, dtype):
+    """One row and nine: a lane-group kernel (D 144: two rows a wave and trip forward, sixteen a workgroup) and a
+    one-row-per-wave kernel (D 512: eight rows a workgroup forward) with a partial wave, slot and workgroup, under
+    test_layernorm's bounds."""
+    _check_layernorm(D, M, dtype)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_layernorm_misaligned_x_runs_generic(dtype):
+    """x four bytes off a 16-byte boundary at D 512, M 37: the plan is GENERIC in both directions (no 16-byte vector
+    may touch x), the results hold test_layernorm's bounds, and the 64 bytes either side of y and of dx stay as they
+    were."""
+    D, M = 512, 37
+    x, gamma, beta, dy, dres, yr, dxr, dgr, dbr = _layernorm_case(D, M)
+    xd = torch.empty(M * D + 4, device=DEV)[1:M * D + 1].view(M, D)
+    xd.copy_(x)
+    assert xd.data_ptr() % 16 == 4
+    for op in (_lib.LN_FWD, _lib.LN_BWD):
+        dt = _lib.BF16 if dtype == torch.bfloat16 else _lib.F32
+        q, c = _lib.LnQuery(op=op, D=D, M=M, x_mod16=xd.data_ptr() % 16, dt_y=dt, dt_dy=dt), _lib.LnChoice()
+        _lib.call("cfm_layernorm_plan", q, c)
+        assert c.family == _lib.LN_GENERIC
+
+    def guarded(dt):
+        """M x D of dt with 64 sentinel bytes before and after: (buffer as bytes, the tensor)"""
+        es = torch.empty(0, dtype=dt).element_size()
+        buf = torch.full((128 + M * D * es,), 0xA5, dtype=torch.uint8, device=DEV)
+        return buf, buf[64:64 + M * D * es].view(dt).view(M, D)
+
+    def untouched(buf):
+        return bool((buf[:64] == 0xA5).all()) and bool((buf[-64:] == 0xA5).all())
+    gm, bt = gamma.to(DEV), beta.to(DEV)
+    ybuf, y = guarded(dtype)
+    mean, rstd = torch.empty(M, device=DEV), torch.empty(M, device=DEV)
+    _lib.call("cfm_layernorm_fwd", _lib.ptr(xd), _lib.dt(xd), _lib.ptr(gm), _lib.ptr(bt), _lib.ptr(y), _lib.dt(y),
+              _lib.ptr(mean), _lib.ptr(rstd), M, D, 1e-5, _lib.stream())
+    dxbuf, dx = guarded(torch.float32)
+    dyd, dresd = dy.to(DEV, dtype), dres.to(DEV)
+    gb = torch.empty(2, D, device=DEV)
+    ws = torch.empty(_lib.size_call("cfm_layernorm_ws_bytes", M, D), dtype=torch.uint8, device=DEV)
+    _lib.call("cfm_layernorm_bwd", _lib.ptr(dyd), _lib.dt(dyd), _lib.ptr(xd), _lib.dt(xd), _lib.ptr(gm),
+              _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(dresd), _lib.dt(dresd), _lib.ptr(dx), _lib.dt(dx),
+              _lib.ptr(gb[0]), _lib.ptr(gb[1]), _lib.ptr(ws), M, D, _lib.stream())
+    torch.cuda.synchronize()
+    assert untouched(ybuf) and untouched(dxbuf)
+    assert _rel(y, yr) < (1e-6 if dtype == torch.float32 else 5e-3)
+    tol = 1e-5 if dtype == torch.float32 else 1e-2
+    assert _rel(dx, dxr) < tol
+    assert _rel(gb[0], dgr) < tol
+    assert _rel(gb[1], dbr) < tol
 
 
 def test_specaug_bit_exact_vs_oracle(golden_dir):
