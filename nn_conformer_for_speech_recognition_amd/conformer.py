@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import math
 import os
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -68,15 +69,16 @@ class _ConvParams(nn.Module):
             nn.Conv1d(d, d, 1, bias=True), nn.Dropout(dropout))
 
 
-def rel_pos_table(T, d, device):
+def rel_pos_table(T, d, device, dtype=None):
     """(2T-1, d) sinusoid, row r <-> relative position (T-1)-r (transformers
-    modeling_wav2vec2_conformer.py:168-205).  Built on the host once per length (cached)."""
+    modeling_wav2vec2_conformer.py:168-205).  Built on the host once per length (cached); plain torch ops, so the
+    compiled route traces it too (dtype: cast in the same .to() as the move to the device)."""
     pos = torch.arange(T - 1, -T, -1, dtype=torch.int64).float().unsqueeze(1)
     div = torch.exp(torch.arange(0, d, 2, dtype=torch.int64).float() * -(math.log(10000.0) / d))
     pe = torch.zeros(2 * T - 1, d)
     pe[:, 0::2] = torch.sin(pos * div)
     pe[:, 1::2] = torch.cos(pos * div)
-    return pe.to(device)
+    return pe.to(device=device, dtype=dtype)
 
 
 # parameter order of one layer (the autograd node's inputs after x)
@@ -95,6 +97,39 @@ _PNAMES = [
     "final_layer_norm.weight", "final_layer_norm.bias",
 ]
 _REL_PNAMES = ["self_attn.linear_pos.weight", "self_attn.pos_bias_u", "self_attn.pos_bias_v"]
+
+# Where each module's parameters sit in that list: a slot is the position of a weight (a LayerNorm / norm gamma or a
+# weight matrix), looked up by name, and its bias FOLLOWS it (bias_of).  Every other place that addresses a layer
+# parameter, a gradient, a shadow or a gradient-bucket view goes through these records.
+_FFNSlots = namedtuple("_FFNSlots", "ln up down")
+_MHASlots = namedtuple("_MHASlots", "ln qkv out")
+_ConvSlots = namedtuple("_ConvSlots", "ln pw1 dw norm pw2")
+_RelSlots = namedtuple("_RelSlots", "pos u v")       # positions in the rel tail, params[REL_TAIL:]
+
+
+def _slots(cls, *names):
+    return cls(*(_PNAMES.index(n) for n in names))
+
+
+def bias_of(slot):
+    return slot + 1
+
+
+FFN1 = _slots(_FFNSlots, *(f"ffn1.sequential.{k}.weight" for k in (0, 1, 4)))
+MHA = _slots(_MHASlots, "self_attn_layer_norm.weight", "self_attn.in_proj_weight", "self_attn.out_proj.weight")
+CONV = _slots(_ConvSlots, "conv_module.layer_norm.weight",
+              *(f"conv_module.sequential.{k}.weight" for k in (0, 2, 3, 5)))
+FFN2 = _slots(_FFNSlots, *(f"ffn2.sequential.{k}.weight" for k in (0, 1, 4)))
+FINAL_LN = _PNAMES.index("final_layer_norm.weight")
+REL_TAIL = len(_PNAMES)
+REL = _RelSlots(*(_REL_PNAMES.index(f"self_attn.{n}") for n in ("linear_pos.weight", "pos_bias_u", "pos_bias_v")))
+# weights of the forward GEMMs that run on fp8 in fp8 mode: FFN up/down (both FFNs), QKV, out-projection
+FP8_W = (FFN1.up, FFN1.down, MHA.qkv, MHA.out, FFN2.up, FFN2.down)
+# the 2-D (and pointwise-conv) weight matrices: cast to the compute dtype once per step ...
+CAST_W = tuple(sorted(FP8_W + (CONV.pw1, CONV.pw2)))
+# ... and the weights whose gradients (with the following bias) the grouped weight-gradient launch produces -- the
+# bulk of every layer's gradient bytes, which dist.GradAllReducer keeps in its buckets
+GROUPED_W = CAST_W
 
 
 # rel-pos: all layers' projected tables from one batched GEMM, dW_pos in the grouped weight-gradient launch
@@ -126,15 +161,15 @@ LN_PAIR = os.environ.get("CFM_LN_PAIR", "1") != "0"
 
 class _Cfg:
     __slots__ = ("B", "T", "d", "H", "ffn", "K", "p", "cd", "training", "conv_first", "rel", "seed",
-                 "bn_rm", "bn_rv", "bn_mom", "pe", "shadow", "shadow_t", "group_wgrad", "layer_index",
-                 "grad_dest", "flush_here", "on_flushed", "on_routed", "sync_bn", "shadow8", "pos_pre", "rdt", "rfuse",
+                 "bn_rm", "bn_rv", "bn_mom", "pe", "shadow", "group_wgrad", "layer_index",
+                 "grad_dest", "flush_here", "on_flushed", "on_routed", "sync_bn", "pos_pre", "rdt", "rfuse",
                  "gn", "gn_eps")
 
 
-# the 2-D (and pointwise-conv) weight matrices of _PNAMES: cast to the compute dtype once per step
-_WIDX = (2, 4, 8, 10, 14, 20, 24, 26)
-# weights of the forward GEMMs that run on fp8 in fp8 mode: FFN up/down (both FFNs), QKV, out-projection
-_FP8_W = (2, 4, 8, 10, 24, 26)
+# one layer's per-step weight copies, each {slot: ...} and empty where absent (Conformer._shadows): compute-dtype
+# copies, their transposed K-major copies, (fp8 copy, its dequantisation scales)
+_Shadow = namedtuple("_Shadow", "plain t fp8")
+_NO_SHADOW = _Shadow({}, {}, {})
 # fp8 scaling: MX block scales (default) or per-tensor current scaling (CFM_FP8_SCALING=tensor, A/B)
 FP8_MX = os.environ.get("CFM_FP8_SCALING", "mx") != "tensor"
 
@@ -158,7 +193,7 @@ class _Side:
         self.side = _SIDE_STREAMS[key]
         self.keep = []
         self.group = None      # ops.WgradGroup when this layer's weight gradients are deferred
-        self.dest = None       # {weight index: (dW view, db view)} in a data-parallel gradient bucket
+        self.dest = None       # {weight slot: (dW view, db view)} in a data-parallel gradient bucket
         self.rgroup = None     # ops.ReduceGroup: this layer's small column reductions, deferred likewise
         self.routed = 0        # grouped weight gradients written straight into their bucket views
 
@@ -190,7 +225,7 @@ def _has_grad_hooks(p):
 
 def _wgrad_bias(side, dy, x, widx=None):
     """(dW, db) = (dyᵀ·x, Σ_rows dy): queued for the grouped launch (side.group) when the layer defers its
-    weight gradients, else on the side stream (outputs allocated on the main stream).  widx: _PNAMES index
+    weight gradients, else on the side stream (outputs allocated on the main stream).  widx: slot
     of the weight; with a data-parallel gradient bucket attached (side.dest, dist.GradAllReducer) the
     grouped launch writes straight into the bucket (autograd adopts the returned views as .grad)."""
     if side.group is not None and ops.wgrad_group_ok(dy, x):
@@ -211,11 +246,11 @@ def _w(t, cd):
 
 def _wt(cfg, i):
     """K-major (transposed) compute-dtype copy of weight matrix i, if the shadows carry one."""
-    return cfg.shadow_t.get(i) if cfg.shadow_t else None
+    return cfg.shadow.t.get(i)
 
 
 def _fp8_on(cfg, i, K):
-    return bool(cfg.shadow8) and i in cfg.shadow8 and K % 128 == 0
+    return i in cfg.shadow.fp8 and K % 128 == 0
 
 
 def _ln_fwd(x, P, i, cfg, fp8_w=None, d=None):
@@ -223,16 +258,17 @@ def _ln_fwd(x, P, i, cfg, fp8_w=None, d=None):
     writes the MX copy of its bf16 output (cfm_layernorm_fwd_mx).  d: the previous module's pending output (RES_FUSE)
     -- the module input is then x + d, formed here.  -> (xn, (xn8, s8) or None, mu, rs, module input)"""
     mx = fp8_w is not None and FP8_MX and cfg.cd == torch.bfloat16 and _fp8_on(cfg, fp8_w, x.shape[1])
+    gamma, beta = P[i], P[bias_of(i)]
     if d is not None:
         if mx:
-            x, xn, q, mu, rs = ops.layernorm_fwd_res(x, d, P[i], P[i + 1], _EPS, mx=True)
+            x, xn, q, mu, rs = ops.layernorm_fwd_res(x, d, gamma, beta, _EPS, mx=True)
             return xn, q, mu, rs, x
-        x, xn, mu, rs = ops.layernorm_fwd_res(x, d, P[i], P[i + 1], _EPS, out_dtype=cfg.cd)
+        x, xn, mu, rs = ops.layernorm_fwd_res(x, d, gamma, beta, _EPS, out_dtype=cfg.cd)
         return xn, None, mu, rs, x
     if mx:
-        xn, q, mu, rs = ops.layernorm_fwd_mx(x, P[i], P[i + 1], _EPS)
+        xn, q, mu, rs = ops.layernorm_fwd_mx(x, gamma, beta, _EPS)
         return xn, q, mu, rs, x
-    xn, mu, rs = ops.layernorm_fwd(x, P[i], P[i + 1], _EPS, out_dtype=cfg.cd)
+    xn, mu, rs = ops.layernorm_fwd(x, gamma, beta, _EPS, out_dtype=cfg.cd)
     return xn, None, mu, rs, x
 
 
@@ -241,45 +277,42 @@ def _res_kw(cfg, x):
     return {"out_dtype": torch.bfloat16} if cfg.rfuse else {"out_dtype": cfg.rdt, "residual": x}
 
 
-def _fp8_linear(x, cfg, i, xq=None, **kw):
-    """Forward GEMM with fp8 (e4m3fn) operands when the layer runs the fp8 path (BASELINE.json configs[4]):
-    x quantised on the device -- MX block scales (one e8m0 per 32 K-elements, one pass, applied inside the
-    block-scaled MFMA), or per tensor with CFM_FP8_SCALING=tensor (A/B) -- weight i from the per-step fp8 shadow;
-    else None.  The backward keeps the bf16 operands (x, the bf16 weight shadow)."""
+def _linear(x, w, P, i, cfg, xq=None, **kw):
+    """Forward GEMM of weight slot i with its bias; w: the compute-dtype weight.  With fp8 (e4m3fn) operands when the
+    layer runs the fp8 path (BASELINE.json configs[4]): x quantised on the device (xq: its MX copy where a producer
+    kernel already wrote one) -- MX block scales (one e8m0 per 32 K-elements, one pass, applied inside the block-scaled
+    MFMA), or per tensor with CFM_FP8_SCALING=tensor (A/B) -- weight i from the per-step fp8 shadow.  The backward
+    keeps the bf16 operands (x, the bf16 weight shadow)."""
+    bias = P[bias_of(i)]
     if not _fp8_on(cfg, i, x.shape[1]):
-        return None
-    wq, sw = cfg.shadow8[i]
+        return ops.linear(x, w, bias, **kw)
+    wq, sw = cfg.shadow.fp8[i]
     if FP8_MX:
         x8, sx = xq if xq is not None else ops.quant_mx(x)
-        return ops.linear(x8, wq, x_mx=sx, w_mx=sw, **kw)
-    xq, sx = ops.quant_fp8(x)
-    return ops.linear(xq, wq, x_scale=sx, w_scale=sw, **kw)
+        return ops.linear(x8, wq, bias, x_mx=sx, w_mx=sw, **kw)
+    x8, sx = ops.quant_fp8(x)
+    return ops.linear(x8, wq, bias, x_scale=sx, w_scale=sw, **kw)
 
 
-def _ffn_fwd(x, P, o, cfg, seed, d=None, xn=None):
+def _ffn_fwd(m, x, P, R, cfg, lens, d=None, xn=None):
     """-> (the new stream, or the bf16 module output under RES_FUSE; saved tensors; the module input).
+    d: the previous module's pending output (RES_FUSE, see _ln_fwd).
     xn: the module-input LayerNorm's output when the layer below already computed it (LN_PAIR)."""
-    cd = cfg.cd
+    cd, o, seed = cfg.cd, m.slots, cfg.seed + m.seed
     if xn is not None:
         xq = mu = rs = None
     else:
-        xn, xq, mu, rs, x = _ln_fwd(x, P, o, cfg, o + 2, d)
-    w1, w2 = _w(P[o + 2], cd), _w(P[o + 4], cd)
+        xn, xq, mu, rs, x = _ln_fwd(x, P, o.ln, cfg, o.up, d)
+    w1, w2 = _w(P[o.up], cd), _w(P[o.down], cd)
     pre = torch.empty(x.shape[0], cfg.ffn, device=x.device, dtype=cd)
     # MX fp8 for both FFN GEMMs: the up-projection's epilogue also writes the MX copy of h (the down GEMM's operand)
     hq = None
-    if FP8_MX and _fp8_on(cfg, o + 2, xn.shape[1]) and _fp8_on(cfg, o + 4, cfg.ffn) and cfg.ffn % 32 == 0:
+    if FP8_MX and _fp8_on(cfg, o.up, xn.shape[1]) and _fp8_on(cfg, o.down, cfg.ffn) and cfg.ffn % 32 == 0:
         hq = (torch.empty(x.shape[0], cfg.ffn, device=x.device, dtype=torch.float8_e4m3fn),
               torch.empty(x.shape[0], cfg.ffn // 32, device=x.device, dtype=torch.uint8))
-    h = _fp8_linear(xn, cfg, o + 2, xq=xq, bias=P[o + 3], act=ACT_SILU, pre=pre, drop_p=cfg.p, seed=seed,
-                    **({"mx_out": hq} if hq is not None else {}))
-    if h is None:
-        h = ops.linear(xn, w1, P[o + 3], act=ACT_SILU, pre=pre, drop_p=cfg.p, seed=seed)
-    y = _fp8_linear(h, cfg, o + 4, xq=hq, bias=P[o + 5], drop_p=cfg.p, seed=seed + 1, out_scale=0.5,
-                    **_res_kw(cfg, x))
-    if y is None:
-        y = ops.linear(h, w2, P[o + 5], drop_p=cfg.p, seed=seed + 1, out_scale=0.5, **_res_kw(cfg, x))
-    _chk(f"ffn{o}_fwd", xn, mu, rs, pre, h, y)
+    h = _linear(xn, w1, P, o.up, cfg, xq, act=ACT_SILU, pre=pre, drop_p=cfg.p, seed=seed, mx_out=hq)
+    y = _linear(h, w2, P, o.down, cfg, hq, drop_p=cfg.p, seed=seed + 1, out_scale=0.5, **_res_kw(cfg, x))
+    _chk(f"{m.name}_fwd", xn, mu, rs, pre, h, y)
     return y, (xn, mu, rs, pre, h, w1, w2), x
 
 
@@ -289,73 +322,75 @@ def _in_drop(kind, cfg, seed):
     return {"ffn": (0.5, cfg.p, seed + 1), "mha": (1.0, cfg.p, seed + 1), "conv": (1.0, cfg.p, seed)}[kind] + (cfg.cd,)
 
 
-def _g2(g, g2, kind, cfg, seed):
+def _g2(g, g2, m, cfg):
     if g2 is not None:
         return g2
-    sc, p, sd, cd = _in_drop(kind, cfg, seed)
+    sc, p, sd, cd = _in_drop(m.kind, cfg, cfg.seed + m.seed)
     return ops.scale_dropout(g, sc, p, sd, 0, out_dtype=cd)
 
 
-def _ln_bwd(dxn, x, P, i, mu, rs, g, side, nxt):
-    """module-input LayerNorm backward (+ residual g); nxt: the next module's _in_drop (or None) ->
-    its g2 comes out of the same kernel.  Returns (dx, g2_next)."""
+def _ln_bwd(dxn, x, P, i, mu, rs, g, side, nxt, grads):
+    """LayerNorm backward (+ residual g) of slot i, its parameter gradients into grads; nxt: the _in_drop (or None)
+    of the module that runs backward next -> its g2 comes out of the same kernel.  Returns (dx, g2_next)."""
     if nxt is None:
-        dx, gg, gb = ops.layernorm_bwd(dxn, x, P[i], mu, rs, dres=g, side=side)
-        g2n = None
-    else:
-        dx, gg, gb, g2n = ops.layernorm_bwd(dxn, x, P[i], mu, rs, dres=g, side=side, drop=nxt)
-    return dx, gg, gb, g2n
-
-
-def _ffn_bwd(g, x, sv, P, o, cfg, seed, grads, side, g2=None, nxt=None):
-    xn, mu, rs, pre, h, w1, w2 = sv
-    cd = cfg.cd
-    g2 = _g2(g, g2, "ffn", cfg, seed)
-    grads[o + 4], grads[o + 5] = _wgrad_bias(side, g2, h, o + 4)
-    da = ops.linear_dgrad(g2, w2, pre=pre, act_grad=True, drop_p=cfg.p, seed=seed, wt=_wt(cfg, o + 4))
-    grads[o + 2], grads[o + 3] = _wgrad_bias(side, da, xn, o + 2)
-    dxn = ops.linear_dgrad(da, w1, wt=_wt(cfg, o + 2))
-    if mu is None:
-        # the module-input LayerNorm ran in the layer below (LN_PAIR) and so does its backward: hand it the stream
-        # gradient and the gradient of the normalised input apart
-        _chk(f"ffn{o}_bwd", g2, da, dxn)
-        return g, dxn
-    dx, grads[o], grads[o + 1], g2n = _ln_bwd(dxn, x, P, o, mu, rs, g, side, nxt)
-    _chk(f"ffn{o}_bwd", g2, da, dxn, dx, g2n)
+        dx, grads[i], grads[bias_of(i)] = ops.layernorm_bwd(dxn, x, P[i], mu, rs, dres=g, side=side)
+        return dx, None
+    dx, grads[i], grads[bias_of(i)], g2n = ops.layernorm_bwd(dxn, x, P[i], mu, rs, dres=g, side=side, drop=nxt)
     return dx, g2n
 
 
-def _mha_fwd(x, P, R, cfg, seed, lens, dprev=None):
-    cd = cfg.cd
-    B, T, d, H = cfg.B, cfg.T, cfg.d, cfg.H
-    xn, xq, mu, rs, x = _ln_fwd(x, P, 6, cfg, 8, dprev)
-    win, wout = _w(P[8], cd), _w(P[10], cd)
-    qkv = _fp8_linear(xn, cfg, 8, xq=xq, bias=P[9])
-    if qkv is None:
-        qkv = ops.linear(xn, win, P[9])
+def _wgrad_into(grads, side, dy, x, i, shape=None):
+    """weight slot i's (dW, db) into grads (dW viewed as `shape`: the pointwise convs' (N, K, 1))"""
+    dw, grads[bias_of(i)] = _wgrad_bias(side, dy, x, i)
+    grads[i] = dw if shape is None else dw.view(shape)
+
+
+def _ffn_bwd(m, g, x, sv, P, R, cfg, lens, grads, rgrads, side, g2=None, nxt=None):
+    """-> (the gradient of the module input, the g2 of the module that runs backward next)"""
+    xn, mu, rs, pre, h, w1, w2 = sv
+    o, seed = m.slots, cfg.seed + m.seed
+    g2 = _g2(g, g2, m, cfg)
+    _wgrad_into(grads, side, g2, h, o.down)
+    da = ops.linear_dgrad(g2, w2, pre=pre, act_grad=True, drop_p=cfg.p, seed=seed, wt=_wt(cfg, o.down))
+    _wgrad_into(grads, side, da, xn, o.up)
+    dxn = ops.linear_dgrad(da, w1, wt=_wt(cfg, o.up))
+    if mu is None:
+        # the module-input LayerNorm ran in the layer below (LN_PAIR) and so does its backward: hand it the stream
+        # gradient and the gradient of the normalised input apart
+        _chk(f"{m.name}_bwd", g2, da, dxn)
+        return g, dxn
+    dx, g2n = _ln_bwd(dxn, x, P, o.ln, mu, rs, g, side, nxt, grads)
+    _chk(f"{m.name}_bwd", g2, da, dxn, dx, g2n)
+    return dx, g2n
+
+
+def _mha_fwd(m, x, P, R, cfg, lens, d=None, xn=None):
+    cd, s, seed = cfg.cd, m.slots, cfg.seed + m.seed
+    B, T, H = cfg.B, cfg.T, cfg.H
+    xn, xq, mu, rs, x = _ln_fwd(x, P, s.ln, cfg, s.qkv, d)
+    win, wout = _w(P[s.qkv], cd), _w(P[s.out], cd)
+    qkv = _linear(xn, win, P, s.qkv, cfg, xq)
     pos = pu = pv = None
     if cfg.rel:
         if cfg.pos_pre is not None:     # this layer's slice of Conformer._rel_tables' one batched projection
             pos = cfg.pos_pre
         else:
-            pos = ops.linear(_w(cfg.pe, cd), _w(R[0], cd))      # (2T-1, d) projected table (no bias)
-        pu = R[1].reshape(-1).float().contiguous()
-        pv = R[2].reshape(-1).float().contiguous()
-    o, lse = ops.attn_fwd(qkv, lens, B, T, H, d // H, pos, pu, pv, drop_p=cfg.p, seed=seed)
-    y = _fp8_linear(o, cfg, 10, bias=P[11], drop_p=cfg.p, seed=seed + 1, **_res_kw(cfg, x))
-    if y is None:
-        y = ops.linear(o, wout, P[11], drop_p=cfg.p, seed=seed + 1, **_res_kw(cfg, x))
-    _chk("mha_fwd", xn, mu, rs, qkv, pos, o, lse, y)
+            pos = ops.linear(_w(cfg.pe, cd), _w(R[REL.pos], cd))      # (2T-1, d) projected table (no bias)
+        pu = R[REL.u].reshape(-1).float().contiguous()
+        pv = R[REL.v].reshape(-1).float().contiguous()
+    o, lse = ops.attn_fwd(qkv, lens, B, T, H, cfg.d // H, pos, pu, pv, drop_p=cfg.p, seed=seed)
+    y = _linear(o, wout, P, s.out, cfg, drop_p=cfg.p, seed=seed + 1, **_res_kw(cfg, x))
+    _chk(f"{m.name}_fwd", xn, mu, rs, qkv, pos, o, lse, y)
     return y, (xn, mu, rs, qkv, o, lse, win, wout, pos, pu, pv), x
 
 
-def _mha_bwd(g, x, sv, P, R, cfg, seed, lens, grads, rgrads, side, g2=None, nxt=None):
+def _mha_bwd(m, g, x, sv, P, R, cfg, lens, grads, rgrads, side, g2=None, nxt=None):
     xn, mu, rs, qkv, o, lse, win, wout, pos, pu, pv = sv
-    cd = cfg.cd
+    cd, s, seed = cfg.cd, m.slots, cfg.seed + m.seed
     B, T, d, H = cfg.B, cfg.T, cfg.d, cfg.H
-    g4 = _g2(g, g2, "mha", cfg, seed)
-    grads[10], grads[11] = _wgrad_bias(side, g4, o, 10)
-    wt = _wt(cfg, 10)
+    g4 = _g2(g, g2, m, cfg)
+    _wgrad_into(grads, side, g4, o, s.out)
+    wt = _wt(cfg, s.out)
     aws = None
     if wt is not None and d // H == 64 and cd == torch.bfloat16 and "rowdot" not in ops.DISABLED:
         # D = rowsum(dO * O) per head from the epilogue of the GEMM producing dO (no separate pass); rel-pos: written
@@ -375,61 +410,75 @@ def _mha_bwd(g, x, sv, P, R, cfg, seed, lens, grads, rgrads, side, g2=None, nxt=
         if REL_BATCH and side.group is not None and ops.wgrad_group_ok(dpc, pec):
             # dW_pos = dposᵀ·pe as one more task of the grouped weight-gradient launch (M = 2T-1 rows; its bias
             # sums are not used) -- alone it ran on 16 workgroups (L60: 30 us per layer)
-            rgrads[0], _ = side.group.add(dpc, pec)
+            rgrads[REL.pos], _ = side.group.add(dpc, pec)
         else:
-            rgrads[0] = ops.linear_wgrad(dpc, pec)
-        rgrads[1] = dpu.view(H, d // H)
-        rgrads[2] = dpv.view(H, d // H)
-    grads[8], grads[9] = _wgrad_bias(side, dqkv, xn, 8)
-    dxn = ops.linear_dgrad(dqkv, win, wt=_wt(cfg, 8))
-    dx, grads[6], grads[7], g2n = _ln_bwd(dxn, x, P, 6, mu, rs, g, side, nxt)
-    _chk("mha_bwd", g4, do, Dh, dqkv, dpos, dxn, dx, g2n)
+            rgrads[REL.pos] = ops.linear_wgrad(dpc, pec)
+        rgrads[REL.u] = dpu.view(H, d // H)
+        rgrads[REL.v] = dpv.view(H, d // H)
+    _wgrad_into(grads, side, dqkv, xn, s.qkv)
+    dxn = ops.linear_dgrad(dqkv, win, wt=_wt(cfg, s.qkv))
+    dx, g2n = _ln_bwd(dxn, x, P, s.ln, mu, rs, g, side, nxt, grads)
+    _chk(f"{m.name}_bwd", g4, do, Dh, dqkv, dpos, dxn, dx, g2n)
     return dx, g2n
 
 
-def _conv_fwd(x, P, cfg, seed, dprev=None):
-    cd = cfg.cd
-    B, T, d, K = cfg.B, cfg.T, cfg.d, cfg.K
-    xn, _, mu, rs, x = _ln_fwd(x, P, 12, cfg, None, dprev)
-    wp1, wp2 = _w(P[14].view(2 * d, d), cd), _w(P[20].view(d, d), cd)
-    wdw = P[16].view(d, K)
-    a = ops.linear(xn, wp1, P[15])
-    ws = ops.convmod_ws(B, T, d, K, x.device)
-    yv = ops.glu_dwconv_fwd(a, wdw, P[17], B, T, d, K, ws)
+def _conv_fwd(m, x, P, R, cfg, lens, d=None, xn=None):
+    cd, s, seed = cfg.cd, m.slots, cfg.seed + m.seed
+    B, T, C, K = cfg.B, cfg.T, cfg.d, cfg.K
+    xn, _, mu, rs, x = _ln_fwd(x, P, s.ln, cfg, None, d)
+    wp1, wp2 = _w(P[s.pw1].view(2 * C, C), cd), _w(P[s.pw2].view(C, C), cd)
+    wdw = P[s.dw].view(C, K)
+    gamma, beta = P[s.norm], P[bias_of(s.norm)]
+    a = _linear(xn, wp1, P, s.pw1, cfg)
+    ws = ops.convmod_ws(B, T, C, K, x.device)
+    yv = ops.glu_dwconv_fwd(a, wdw, P[bias_of(s.dw)], B, T, C, K, ws)
     if cfg.gn:      # GroupNorm(1, d): per-utterance statistics (B,), the same function in train and eval
-        z, bmean, binv = ops.gn_silu_fwd(yv, P[18], P[19], cfg.gn_eps, B, T, d, ws, cd)
+        z, bmean, binv = ops.gn_silu_fwd(yv, gamma, beta, cfg.gn_eps, B, T, C, ws, cd)
     elif cfg.sync_bn is not None and cfg.training:
-        z, bmean, binv = ops.bn_silu_fwd_sync(yv, P[18], P[19], cfg.bn_rm, cfg.bn_rv, cfg.bn_mom, _EPS, B, T, d, ws,
+        z, bmean, binv = ops.bn_silu_fwd_sync(yv, gamma, beta, cfg.bn_rm, cfg.bn_rv, cfg.bn_mom, _EPS, B, T, C, ws,
                                               cd, cfg.sync_bn[0], cfg.sync_bn[1])
     else:
-        z, bmean, binv = ops.bn_silu_fwd(yv, P[18], P[19], cfg.bn_rm, cfg.bn_rv, cfg.bn_mom, _EPS, cfg.training, B,
-                                         T, d, ws, cd)
-    y = ops.linear(z, wp2, P[21], drop_p=cfg.p, seed=seed, **_res_kw(cfg, x))
-    _chk("conv_fwd", xn, mu, rs, a, yv, bmean, binv, z, y)
+        z, bmean, binv = ops.bn_silu_fwd(yv, gamma, beta, cfg.bn_rm, cfg.bn_rv, cfg.bn_mom, _EPS, cfg.training, B,
+                                         T, C, ws, cd)
+    y = _linear(z, wp2, P, s.pw2, cfg, drop_p=cfg.p, seed=seed, **_res_kw(cfg, x))
+    _chk(f"{m.name}_fwd", xn, mu, rs, a, yv, bmean, binv, z, y)
     return y, (xn, mu, rs, a, yv, z, bmean, binv, wp1, wp2, wdw), x
 
 
-def _conv_bwd(g, x, sv, P, cfg, seed, grads, side, g2=None, nxt=None):
+def _conv_bwd(m, g, x, sv, P, R, cfg, lens, grads, rgrads, side, g2=None, nxt=None):
     xn, mu, rs, a, yv, z, bmean, binv, wp1, wp2, wdw = sv
-    cd = cfg.cd
-    B, T, d, K = cfg.B, cfg.T, cfg.d, cfg.K
-    g3 = _g2(g, g2, "conv", cfg, seed)
-    dw, grads[21] = _wgrad_bias(side, g3, z, 20)
-    grads[20] = dw.view(d, d, 1)
-    dz = ops.linear_dgrad(g3, wp2, wt=_wt(cfg, 20))
-    ws = ops.convmod_ws(B, T, d, K, x.device)
+    cd, s = cfg.cd, m.slots
+    B, T, C, K = cfg.B, cfg.T, cfg.d, cfg.K
+    g3 = _g2(g, g2, m, cfg)
+    _wgrad_into(grads, side, g3, z, s.pw2, (C, C, 1))
+    dz = ops.linear_dgrad(g3, wp2, wt=_wt(cfg, s.pw2))
+    ws = ops.convmod_ws(B, T, C, K, x.device)
     sync = cfg.sync_bn is not None and cfg.training
-    da, dwdw, grads[17], grads[18], grads[19], dy = ops.norm_silu_glu_dwconv_bwd(
-        "gn" if cfg.gn else "bn", dz, yv, P[18], P[19], bmean, binv, cfg.training, a, wdw, B, T, d, K, ws, cd,
-        side=side, reduce_sums=cfg.sync_bn[0] if sync else None, world=cfg.sync_bn[1] if sync else 1,
+    da, dwdw, grads[bias_of(s.dw)], dgamma, dbeta, dy = ops.norm_silu_glu_dwconv_bwd(
+        "gn" if cfg.gn else "bn", dz, yv, P[s.norm], P[bias_of(s.norm)], bmean, binv, cfg.training, a, wdw, B, T, C,
+        K, ws, cd, side=side, reduce_sums=cfg.sync_bn[0] if sync else None, world=cfg.sync_bn[1] if sync else 1,
         fold="bnfold" not in ops.DISABLED)     # (CFM_DISABLE=bnfold: separate norm backward, A/B)
-    grads[16] = dwdw.view(d, 1, K)
-    dw, grads[15] = _wgrad_bias(side, da, xn, 14)
-    grads[14] = dw.view(2 * d, d, 1)
-    dxn = ops.linear_dgrad(da, wp1, wt=_wt(cfg, 14))
-    dx, grads[12], grads[13], g2n = _ln_bwd(dxn, x, P, 12, mu, rs, g, side, nxt)
-    _chk("conv_bwd", g3, dz, dy, grads[18], grads[19], da, dxn, dx, g2n)
+    grads[s.dw], grads[s.norm], grads[bias_of(s.norm)] = dwdw.view(C, 1, K), dgamma, dbeta
+    _wgrad_into(grads, side, da, xn, s.pw1, (2 * C, C, 1))
+    dxn = ops.linear_dgrad(da, wp1, wt=_wt(cfg, s.pw1))
+    dx, g2n = _ln_bwd(dxn, x, P, s.ln, mu, rs, g, side, nxt, grads)
+    _chk(f"{m.name}_bwd", g3, dz, dy, dgamma, dbeta, da, dxn, dx, g2n)
     return dx, g2n
+
+
+# The four sub-modules of a layer in execution order: parameter slots, the offset of the module's dropout seeds from
+# the layer's, the _in_drop kind of its residual dropout, its forward and backward.  The node (_ConformerLayerFn) and
+# the compiled route (library.layer_forward) both walk module_order().
+_Module = namedtuple("_Module", "name kind slots seed fwd bwd")
+_M_FFN1 = _Module("ffn1", "ffn", FFN1, 0, _ffn_fwd, _ffn_bwd)
+_M_CONV = _Module("conv", "conv", CONV, 10, _conv_fwd, _conv_bwd)
+_M_MHA = _Module("mha", "mha", MHA, 20, _mha_fwd, _mha_bwd)
+_M_FFN2 = _Module("ffn2", "ffn", FFN2, 30, _ffn_fwd, _ffn_bwd)
+_ORDER = {False: (_M_FFN1, _M_MHA, _M_CONV, _M_FFN2), True: (_M_FFN1, _M_CONV, _M_MHA, _M_FFN2)}
+
+
+def module_order(conv_first):
+    return _ORDER[bool(conv_first)]
 
 
 class _ConformerLayerFn(torch.autograd.Function):
@@ -439,52 +488,34 @@ class _ConformerLayerFn(torch.autograd.Function):
     def forward(ctx, x, lens, cfg, xn_in, ng, nb, *params):
         """xn_in: this layer's ffn1 LayerNorm output, computed by the layer below; ng, nb: the ffn1 LayerNorm weight
         and bias of the layer above, whose output this layer then returns beside its own (LN_PAIR; None: plain)."""
-        P = list(params[:len(_PNAMES)])
-        R = params[len(_PNAMES):]
-        if cfg.shadow is not None:       # compute-dtype copies refreshed by Conformer (one launch)
-            for i, t in cfg.shadow[0].items():
-                P[i] = t
-            cfg.shadow_t = cfg.shadow[1]
-            cfg.shadow8 = cfg.shadow[2] if len(cfg.shadow) > 2 else None
-        else:
-            cfg.shadow_t = cfg.shadow8 = None
-        s = cfg.seed
-        x0 = x
-        # each module returns its output (the new stream; under RES_FUSE the pending bf16 module output, added by the
-        # next LayerNorm) and its input, materialised by that LayerNorm -- the tensors the backward saves
-        y1, sv1, _ = _ffn_fwd(x0, P, 0, cfg, s, xn=xn_in)
-        step = (lambda xin, y: (xin, y)) if cfg.rfuse else (lambda xin, y: (y, None))
-        cur = step(x0, y1)
-        if cfg.conv_first:
-            yc, svc, x1 = _conv_fwd(cur[0], P, cfg, s + 10, cur[1])
-            cur = step(x1, yc)
-            ya, sva, xc = _mha_fwd(cur[0], P, R, cfg, s + 20, lens, cur[1])
-            cur = step(xc, ya)
-            chain = (x1, xc)
-        else:
-            ya, sva, x1 = _mha_fwd(cur[0], P, R, cfg, s + 20, lens, cur[1])
-            cur = step(x1, ya)
-            yc, svc, xa = _conv_fwd(cur[0], P, cfg, s + 10, cur[1])
-            cur = step(xa, yc)
-            chain = (x1, xa)
-        y4, sv4, x3 = _ffn_fwd(cur[0], P, 22, cfg, s + 30, cur[1])
-        cur = step(x3, y4)
+        P = list(params[:REL_TAIL])
+        R = params[REL_TAIL:]
+        for i, t in cfg.shadow.plain.items():       # compute-dtype copies refreshed by Conformer (one launch)
+            P[i] = t
+        # each module returns its output (the new stream; under RES_FUSE the pending bf16 module output `pend`, added
+        # by the next LayerNorm) and its input, materialised by that LayerNorm -- the tensors the backward saves
+        pend, xn, ins, svs = None, xn_in, [], []
+        for m in module_order(cfg.conv_first):
+            y, sv, xin = m.fwd(m, x, P, R, cfg, lens, pend, xn)
+            ins.append(xin)
+            svs.append(sv)
+            x, pend = (xin, y) if cfg.rfuse else (y, None)
+            xn = None       # (only ffn1's LayerNorm can have run in the layer below)
+        gamma, beta = P[FINAL_LN], P[bias_of(FINAL_LN)]
         pair = ()
-        if cur[1] is not None:
-            x4, out, mu5, rs5 = ops.layernorm_fwd_res(cur[0], cur[1], P[28], P[29], _EPS, out_dtype=torch.float32)
+        if pend is not None:
+            x, out, mu5, rs5 = ops.layernorm_fwd_res(x, pend, gamma, beta, _EPS, out_dtype=torch.float32)
         elif ng is not None:
-            x4 = cur[0]
-            out, xn_next, mu5, rs5, mu6, rs6 = ops.layernorm_fwd_pair(x4, P[28], P[29], ng, nb, _EPS, out_dtype=cfg.cd)
+            out, xn_next, mu5, rs5, mu6, rs6 = ops.layernorm_fwd_pair(x, gamma, beta, ng, nb, _EPS, out_dtype=cfg.cd)
             pair = (ng, nb, mu6, rs6)
         else:
-            x4 = cur[0]
-            out, mu5, rs5 = ops.layernorm_fwd(x4, P[28], P[29], _EPS, out_dtype=torch.float32)
+            out, mu5, rs5 = ops.layernorm_fwd(x, gamma, beta, _EPS, out_dtype=torch.float32)
         _chk(f"layer{cfg.layer_index}_fwd_out", out, mu5, rs5)
         ctx.cfg = cfg
-        ctx.sv = (sv1, sva, svc, sv4)
+        ctx.sv = svs
         ctx.nparams = len(params)
         ctx.pair_out = bool(pair)
-        ctx.save_for_backward(x0, chain[0], chain[1], x3, x4, mu5, rs5, lens, *params, *pair)
+        ctx.save_for_backward(*ins, x, mu5, rs5, lens, *params, *pair)
         if pair:
             ctx.set_materialize_grads(False)    # a missing gradient of xn_next selects the plain backward
             return out, xn_next
@@ -494,19 +525,18 @@ class _ConformerLayerFn(torch.autograd.Function):
     def backward(ctx, gout, gxn=None):
         cfg = ctx.cfg
         saved = ctx.saved_tensors
-        x0, c0, c1, x3, x4, mu5, rs5, lens = saved[:8]
-        params = saved[8:8 + ctx.nparams]
+        seq = module_order(cfg.conv_first)
+        ins, (x4, mu5, rs5, lens), rest = saved[:len(seq)], saved[len(seq):len(seq) + 4], saved[len(seq) + 4:]
+        params = rest[:ctx.nparams]
         ng = nb = mu6 = rs6 = None
         if ctx.pair_out:
-            ng, nb, mu6, rs6 = saved[8 + ctx.nparams:]
+            ng, nb, mu6, rs6 = rest[ctx.nparams:]
             if gout is None:
                 gout = torch.zeros_like(x4)
-        P = params[:len(_PNAMES)]
-        R = params[len(_PNAMES):]
-        sv1, sva, svc, sv4 = ctx.sv
-        grads = [None] * len(_PNAMES)
+        P = params[:REL_TAIL]
+        R = params[REL_TAIL:]
+        grads = [None] * REL_TAIL
         rgrads = [None] * len(R)
-        s = cfg.seed
         gout = gout.contiguous()
         side = _Side(gout.device)
         # defer this layer's weight-gradient GEMMs into the encoder-wide grouped launch (flushed by layer 0,
@@ -521,31 +551,23 @@ class _ConformerLayerFn(torch.autograd.Function):
             if "rgroup" not in ops.DISABLED:     # (CFM_DISABLE=rgroup: per-layer side-stream reductions, A/B)
                 side.rgroup = _RED_GROUPS.setdefault(str(gout.device), ops.ReduceGroup())
                 side.rgroup.arm_final_flush()
-        # each LayerNorm backward also emits the next module's dropout-scaled input gradient (g2)
-        ffn2_in = _in_drop("ffn", cfg, s + 30)
-        conv_in, mha_in, ffn1_in = _in_drop("conv", cfg, s + 10), _in_drop("mha", cfg, s + 20), _in_drop("ffn", cfg, s)
-        if "lndrop" in ops.DISABLED:
-            ffn2_in = conv_in = mha_in = ffn1_in = None
+        # each LayerNorm backward also emits the dropout-scaled input gradient (g2) of the module before it, the next
+        # to run backward; nothing runs after ffn1  (CFM_DISABLE=lndrop: every module forms its own g2, A/B)
+        drops = [None] + [None if "lndrop" in ops.DISABLED else _in_drop(m.kind, cfg, cfg.seed + m.seed) for m in seq]
         dng = dnb = None
         if gxn is not None:
             # both LayerNorms of the layer boundary in one kernel: gout reaches the stream directly, gxn through the
             # upper layer's ffn1 LayerNorm
-            g, (grads[28], grads[29]), (dng, dnb), g2 = ops.layernorm_bwd_pair(
-                gxn.contiguous(), gout, x4, P[28], P[29], mu5, rs5, ng, mu6, rs6, side=side, drop=ffn2_in)
-        elif ffn2_in is None:
-            (g, grads[28], grads[29]), g2 = ops.layernorm_bwd(gout, x4, P[28], mu5, rs5, side=side), None
+            g, (grads[FINAL_LN], grads[bias_of(FINAL_LN)]), (dng, dnb), g2 = ops.layernorm_bwd_pair(
+                gxn.contiguous(), gout, x4, P[FINAL_LN], P[bias_of(FINAL_LN)], mu5, rs5, ng, mu6, rs6, side=side,
+                drop=drops[-1])
         else:
-            g, grads[28], grads[29], g2 = ops.layernorm_bwd(gout, x4, P[28], mu5, rs5, side=side, drop=ffn2_in)
-        if cfg.conv_first:
-            g, g2 = _ffn_bwd(g, x3, sv4, P, 22, cfg, s + 30, grads, side, g2, mha_in)
-            g, g2 = _mha_bwd(g, c1, sva, P, R, cfg, s + 20, lens, grads, rgrads, side, g2, conv_in)
-            g, g2 = _conv_bwd(g, c0, svc, P, cfg, s + 10, grads, side, g2, ffn1_in)
-        else:
-            g, g2 = _ffn_bwd(g, x3, sv4, P, 22, cfg, s + 30, grads, side, g2, conv_in)
-            g, g2 = _conv_bwd(g, c1, svc, P, cfg, s + 10, grads, side, g2, mha_in)
-            g, g2 = _mha_bwd(g, c0, sva, P, R, cfg, s + 20, lens, grads, rgrads, side, g2, ffn1_in)
-        # (with the ffn1 LayerNorm run by the layer below: g is the stream gradient, gxn_in that of the normalised input)
-        g, gxn_in = _ffn_bwd(g, x0, sv1, P, 0, cfg, s, grads, side, g2, None)
+            g, g2 = _ln_bwd(gout, x4, P, FINAL_LN, mu5, rs5, None, side, drops[-1], grads)
+        # (with the ffn1 LayerNorm run by the layer below, ffn1 returns the stream gradient and, in g2's place, the
+        # gradient of its normalised input)
+        for m, xin, sv, nxt in reversed(list(zip(seq, ins, ctx.sv, drops))):
+            g, g2 = m.bwd(m, g, xin, sv, P, R, cfg, lens, grads, rgrads, side, g2, nxt)
+        gxn_in = g2
         side.join()
         if cfg.on_routed is not None and side.dest and side.routed == len(side.dest):
             cfg.on_routed(cfg.layer_index)       # (data-parallel reducer: this layer's buckets are final at flush)
@@ -585,22 +607,20 @@ class ConformerLayer(nn.Module):
         self.d, self.H, self.ffn, self.K = input_dim, num_attention_heads, ffn_dim, depthwise_conv_kernel_size
 
     def params(self):
+        """The layer's parameters in the node's input order: _PNAMES (+ _REL_PNAMES).  Looked up afresh on every call
+        (a replaced parameter is seen); Conformer.forward_tokens calls it once per layer and hands the list on."""
         sd = dict(self.named_parameters())
-        ps = [sd[n] for n in _PNAMES]
-        if self.pos_enc == "rel":
-            ps += [sd[n] for n in _REL_PNAMES]
-        return ps
+        return [sd[n] for n in (_PNAMES + _REL_PNAMES if self.pos_enc == "rel" else _PNAMES)]
 
     def forward_tokens(self, x, lens_i32, B, T, compute_dtype, seed, pe=None, shadow=None, layer_index=0,
                        group_wgrad=False, grad_dest=None, flush_here=False, on_flushed=None, sync_bn=None,
-                       count_batches=True, on_routed=None, pos_pre=None, xn_in=None, next_ln=None):
-        """x: (B*T, d) fp32 token-major; lens_i32: (B,) int32 on the device; shadow: optional
-        ({param index: compute-dtype copy}, {param index: its transposed K-major copy}) of this
-        layer's weight matrices (see Conformer._shadows).
+                       count_batches=True, on_routed=None, pos_pre=None, xn_in=None, next_ln=None, params=None):
+        """x: (B*T, d) fp32 token-major; lens_i32: (B,) int32 on the device; shadow: optional _Shadow record of this
+        layer's weight matrices (see Conformer._shadows); params: self.params() where the caller already has it.
         LN_PAIR (Conformer.forward_tokens): xn_in is this layer's ffn1 LayerNorm output from the layer below;
         next_ln = (weight, bias) of the next layer's ffn1 LayerNorm -> returns (out, that LayerNorm's output)."""
         cfg = _Cfg()
-        cfg.shadow = shadow
+        cfg.shadow = shadow or _NO_SHADOW
         cfg.B, cfg.T, cfg.d, cfg.H, cfg.ffn, cfg.K = B, T, self.d, self.H, self.ffn, self.K
         cfg.p = float(self.dropout) if self.training else 0.0
         cfg.cd = compute_dtype
@@ -628,7 +648,7 @@ class ConformerLayer(nn.Module):
         if count_batches and self.training and not cfg.gn and bn.track_running_stats:
             bn.num_batches_tracked.add_(1)
         ng, nb = next_ln if next_ln is not None else (None, None)
-        return _ConformerLayerFn.apply(x, lens_i32, cfg, xn_in, ng, nb, *self.params())
+        return _ConformerLayerFn.apply(x, lens_i32, cfg, xn_in, ng, nb, *(params or self.params()))
 
 
 class Conformer(nn.Module):
@@ -664,7 +684,7 @@ class Conformer(nn.Module):
         self._step = 0
         self._shadow = None
         self._q8 = None         # (key, ops.Quant8Batch) of the fp8 forward weights
-        # data-parallel hooks (dist.GradAllReducer.attach): per-layer {weight index: (dW, db) bucket views},
+        # data-parallel hooks (dist.GradAllReducer.attach): per-layer {weight slot (GROUPED_W): (dW, db) bucket views},
         # the layers whose backward flushes the grouped launch, and the callback run after each flush
         self.grad_dest = None
         self.flush_layers = frozenset()
@@ -720,21 +740,22 @@ class Conformer(nn.Module):
                  stride_c=(2 * T - 1) * d)
         return pe_cd, pos_all
 
-    def _shadows(self, device):
-        """Compute-dtype copies of every layer's weight matrices and their transposes, refreshed by
-        ONE cfm_cast_transpose_batch launch per forward (instead of one cast per matrix per layer)."""
+    def _shadows(self, device, plist):
+        """One _Shadow per layer (plist: each layer's params()): compute-dtype copies of its weight matrices and
+        their transposes, refreshed by ONE cfm_cast_transpose_batch launch per forward (instead of one cast per
+        matrix per layer); with fp8=True also the fp8 copies of the forward GEMM weights."""
         if self.compute_dtype == torch.float32:
-            return [None] * len(self.conformer_layers)
-        srcs = [layer.params()[i] for layer in self.conformer_layers for i in _WIDX]
+            return [_NO_SHADOW] * len(plist)
+        srcs = [ps[i] for ps in plist for i in CAST_W]
         key = (str(device), tuple(t.data_ptr() for t in srcs))
         if self._shadow is None or self._shadow[0] != key:
-            n = len(_WIDX)
+            n = len(CAST_W)
             dsts = [torch.empty(t.shape, device=device, dtype=self.compute_dtype) for t in srcs]
             # K-major copies Wᵀ (K, N) for the data-gradient GEMMs (pointwise convs viewed 2-D)
             srcs2 = [t.detach().view(t.shape[0], -1) for t in srcs]   # detached: no autograd view nodes kept alive
             dsts_t = [torch.empty(t.shape[1], t.shape[0], device=device, dtype=self.compute_dtype) for t in srcs2]
-            per = [(dict(zip(_WIDX, dsts[j * n:(j + 1) * n])), dict(zip(_WIDX, dsts_t[j * n:(j + 1) * n])))
-                   for j in range(len(self.conformer_layers))]
+            per = [_Shadow(dict(zip(CAST_W, dsts[j * n:(j + 1) * n])), dict(zip(CAST_W, dsts_t[j * n:(j + 1) * n])), {})
+                   for j in range(len(plist))]
             self._shadow = (key, ops.CastTBatch(srcs2, dsts_t, dsts), per)   # one launch, one read
         self._shadow[1].refresh()
         if not self.fp8:
@@ -742,16 +763,11 @@ class Conformer(nn.Module):
         # per-step fp8 copies (+ dequantisation scalars) of the forward GEMM weights, from the fp32 masters: ONE
         # batched quantisation (two launches for all layers; was two launches per weight)
         if getattr(self, "_q8", None) is None or self._q8[0] != key:
-            srcs8 = [layer.params()[i].detach().view(layer.params()[i].shape[0], -1)
-                     for layer in self.conformer_layers for i in _FP8_W]
+            srcs8 = [ps[i].detach().view(ps[i].shape[0], -1) for ps in plist for i in FP8_W]
             self._q8 = (key, ops.QuantMXBatch(srcs8) if FP8_MX else ops.Quant8Batch(srcs8))
         outs = self._q8[1].refresh()
-        nw = len(_FP8_W)
-        out = []
-        for j, (plain, trans) in enumerate(self._shadow[2]):
-            q8 = dict(zip(_FP8_W, outs[j * nw:(j + 1) * nw]))
-            out.append((plain, trans, q8))
-        return out
+        nw = len(FP8_W)
+        return [sh._replace(fp8=dict(zip(FP8_W, outs[j * nw:(j + 1) * nw]))) for j, sh in enumerate(self._shadow[2])]
 
     def set_sync_batchnorm(self, group=None):
         """torch.nn.SyncBatchNorm semantics for every ConvModule BatchNorm (train mode): batch statistics and
@@ -791,7 +807,8 @@ class Conformer(nn.Module):
                 pe, pos_all = self._rel_tables(T, x.device)
             else:
                 pe = self._pe(T, x.device)
-        shadows = self._shadows(x.device)
+        plist = [layer.params() for layer in self.conformer_layers]    # once per forward: the shadows and the nodes
+        shadows = self._shadows(x.device, plist)
         # grouped weight gradients need layer 0 to run backward last (it flushes the group): true for the
         # sequential encoder; deferral is per layer and falls back when a .grad accumulates
         group = self.compute_dtype == torch.bfloat16
@@ -805,7 +822,7 @@ class Conformer(nn.Module):
                                      flush_here=i in self.flush_layers, on_flushed=self.on_flushed,
                                      sync_bn=self.sync_bn, count_batches=False, on_routed=self.on_routed,
                                      pos_pre=None if pos_all is None else pos_all[i], xn_in=xn,
-                                     next_ln=None if nxt is None else (nxt.weight, nxt.bias))
+                                     next_ln=None if nxt is None else (nxt.weight, nxt.bias), params=plist[i])
             x, xn = x if nxt is not None else (x, None)
         # every layer's BatchNorm num_batches_tracked += 1 in one multi-tensor launch (not one per layer); GroupNorm
         # layers have no counter

@@ -17,6 +17,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from .conformer import GROUPED_W, Conformer, bias_of
+
 
 def init_from_env(backend=None):
     """Initialise the process group from torchrun's env (RANK, WORLD_SIZE, LOCAL_RANK, MASTER_*)."""
@@ -45,11 +47,6 @@ def broadcast_parameters(module, src=0):
     with torch.no_grad():
         for t in list(module.parameters()) + list(module.buffers()):
             dist.broadcast(t.data, src)
-
-
-# _PNAMES indices of the weights whose gradients (with the following bias) the grouped weight-gradient
-# launch produces -- the bulk of every Conformer layer's gradient bytes
-_GROUPED_W = (2, 4, 8, 10, 14, 20, 24, 26)
 
 
 def _avg_op():
@@ -101,8 +98,7 @@ class GradAllReducer:
         self._replay_src = {}
         owned = set()
         if model is not None:
-            from .conformer import Conformer
-            conf = [m for m in model.modules() if isinstance(m, Conformer)]
+            conf =[m for m in model.modules() if isinstance(m, Conformer)]
             if conf and conf[0].compute_dtype == torch.bfloat16:
                 owned = self._attach(conf[0], chunk_layers)
         self.tail = [p for p in self.params if id(p) not in owned]
@@ -135,8 +131,8 @@ class GradAllReducer:
             total = 0
             for li in range(lo, hi):
                 ps = layers[li].params()
-                for wi in _GROUPED_W:
-                    w, b = ps[wi], ps[wi + 1]
+                for wi in GROUPED_W:
+                    w, b = ps[wi], ps[bias_of(wi)]
                     N = w.shape[0]
                     K = w.numel() // N
                     views.append((li, wi, N, K, total, total + (N * K + 63) // 64 * 64))
@@ -244,7 +240,7 @@ class GradAllReducer:
         for li in range(lo, hi):
             ps = self.conformer.conformer_layers[li].params()
             for wi, (dw, db) in self.conformer.grad_dest[li].items():
-                out += [(ps[wi], dw), (ps[wi + 1], db)]
+                out += [(ps[wi], dw), (ps[bias_of(wi)], db)]
         return out
 
     def _adopt(self, chunk, copy):
@@ -287,8 +283,9 @@ class GradAllReducer:
             grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in bucket]
             n = sum(g.numel() for g in grads)
             flat = self._tail_flat[i]
-            if flat is None or flat.numel() != n or flat.device != grads[0].device:
-                flat = torch.empty(n, device=grads[0].device, dtype=torch.float32)
+            dev = bucket[0].device       # (a gradient lives on its parameter's device)
+            if flat is None or flat.numel() != n or flat.device != dev:
+                flat = torch.empty(n, device=dev, dtype=torch.float32)
                 self._tail_flat[i] = flat
             off = 0
             for g in grads:

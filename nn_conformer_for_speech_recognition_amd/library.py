@@ -33,6 +33,7 @@ from torch import Tensor
 
 from . import ops
 from . import _lib as L
+from .conformer import FINAL_LN, REL, REL_TAIL, bias_of, module_order, rel_pos_table
 
 _EPS = 1e-5
 
@@ -294,18 +295,6 @@ def _attn_rel_backward(ctx, go, _glse):
 attention_rel.register_autograd(_attn_rel_backward, setup_context=_attn_rel_setup)
 
 
-def _rel_table(T, d, device, dtype):
-    """The (2T-1, d) sinusoid of conformer.rel_pos_table (the same host ops, so the same values), as traceable
-    torch ops, cast to the compute dtype."""
-    import math
-    pos = torch.arange(T - 1, -T, -1, dtype=torch.int64).float().unsqueeze(1)
-    div = torch.exp(torch.arange(0, d, 2, dtype=torch.int64).float() * -(math.log(10000.0) / d))
-    pe = torch.zeros(2 * T - 1, d)
-    pe[:, 0::2] = torch.sin(pos * div)
-    pe[:, 1::2] = torch.cos(pos * div)
-    return pe.to(device=device, dtype=dtype)
-
-
 # ----------------------------------------------------------------------------- ConvModule middle
 @torch.library.custom_op("cfm::conv_glu_dwconv_bn_silu", mutates_args=(), device_types="cuda")
 def conv_glu_dwconv_bn_silu(a: Tensor, w_dw: Tensor, b_dw: Tensor, gamma: Tensor, beta: Tensor,
@@ -499,40 +488,45 @@ ctc_loss.register_autograd(_ctc_backward, setup_context=_ctc_setup)
 def layer_forward(layer, x, lens, B, T, cd, seed):
     """torchaudio ConformerLayer.forward on x (B*T, d) fp32 token-major, composed of
     torch.ops.cfm.* so FakeTensor / AOTAutograd / torch.compile(fullgraph=True) trace it.  Same kernels,
-    seeds and dropout placement as the fused node in conformer.py; pos_enc='rel' projects the positional table per
+    seeds and dropout placement as the fused node in conformer.py, whose parameter slots and module order
+    (conformer.module_order: the sequence and each module's seed offset) it walks; pos_enc='rel' projects the positional table per
     layer (cfm::linear, dW_pos through its backward) and runs cfm::attention_rel."""
     cfm = torch.ops.cfm
-    P = layer.params()
-    R = P[30:]            # rel-pos: linear_pos.weight, pos_bias_u, pos_bias_v (conformer._REL_PNAMES)
+    params = layer.params()
+    P, R = params[:REL_TAIL], params[REL_TAIL:]
     p = float(layer.dropout) if layer.training else 0.0
     d, H, K = layer.d, layer.H, layer.K
     f32 = torch.float32
 
+    def wb(i):          # (weight, bias) of slot i
+        return P[i], P[bias_of(i)]
+
     def ffn(x, o, s):
-        xn, _, _ = cfm.layer_norm(x, P[o], P[o + 1], _EPS, cd)
-        h, _ = cfm.linear_silu(xn, P[o + 2], P[o + 3], p, s)
-        return cfm.linear(h, P[o + 4], P[o + 5], x, p, s + 1, 0.5, f32)
+        xn, _, _ = cfm.layer_norm(x, *wb(o.ln), _EPS, cd)
+        h, _ = cfm.linear_silu(xn, *wb(o.up), p, s)
+        return cfm.linear(h, *wb(o.down), x, p, s + 1, 0.5, f32)
 
-    def mha(x, s):
-        xn, _, _ = cfm.layer_norm(x, P[6], P[7], _EPS, cd)
-        qkv = cfm.linear(xn, P[8], P[9], None, 0.0, 0, 1.0, cd)
+    def mha(x, o, s):
+        xn, _, _ = cfm.layer_norm(x, *wb(o.ln), _EPS, cd)
+        qkv = cfm.linear(xn, *wb(o.qkv), None, 0.0, 0, 1.0, cd)
         if layer.pos_enc == "rel":
-            pos = cfm.linear(_rel_table(T, d, x.device, cd), R[0], None, None, 0.0, 0, 1.0, cd)
-            o, _ = cfm.attention_rel(qkv, pos, R[1].reshape(-1), R[2].reshape(-1), lens, B, T, H, p, s)
+            pos = cfm.linear(rel_pos_table(T, d, x.device, cd), R[REL.pos], None, None, 0.0, 0, 1.0, cd)
+            a, _ = cfm.attention_rel(qkv, pos, R[REL.u].reshape(-1), R[REL.v].reshape(-1), lens, B, T, H, p, s)
         else:
-            o, _ = cfm.attention(qkv, lens, B, T, H, p, s)
-        return cfm.linear(o, P[10], P[11], x, p, s + 1, 1.0, f32)
+            a, _ = cfm.attention(qkv, lens, B, T, H, p, s)
+        return cfm.linear(a, *wb(o.out), x, p, s + 1, 1.0, f32)
 
-    def conv(x, s):
+    def conv(x, o, s):
         bn = layer.conv_module.sequential[3]
-        xn, _, _ = cfm.layer_norm(x, P[12], P[13], _EPS, cd)
-        a = cfm.linear(xn, P[14].view(2 * d, d), P[15], None, 0.0, 0, 1.0, cd)
+        xn, _, _ = cfm.layer_norm(x, *wb(o.ln), _EPS, cd)
+        a = cfm.linear(xn, P[o.pw1].view(2 * d, d), P[bias_of(o.pw1)], None, 0.0, 0, 1.0, cd)
+        wdw, wp2, bp2 = P[o.dw].view(d, K), P[o.pw2].view(d, d), P[bias_of(o.pw2)]
         if layer.use_group_norm:
-            z = cfm.conv_glu_dwconv_gn_silu(a, P[16].view(d, K), P[17], P[18], P[19], bn.eps, B, cd)[0]
-            return cfm.linear(z, P[20].view(d, d), P[21], x, p, s, 1.0, f32)
+            z = cfm.conv_glu_dwconv_gn_silu(a, wdw, P[bias_of(o.dw)], *wb(o.norm), bn.eps, B, cd)[0]
+            return cfm.linear(z, wp2, bp2, x, p, s, 1.0, f32)
         train = layer.training or not bn.track_running_stats
         z, _, mean, invstd = cfm.conv_glu_dwconv_bn_silu(
-            a, P[16].view(d, K), P[17], P[18], P[19], None if train else bn.running_mean,
+            a, wdw, P[bias_of(o.dw)], *wb(o.norm), None if train else bn.running_mean,
             None if train else bn.running_var, train, bn.eps, B, cd)
         if layer.training and bn.track_running_stats:
             m = bn.momentum if bn.momentum is not None else 0.1
@@ -541,12 +535,9 @@ def layer_forward(layer, x, lens, B, T, cd, seed):
                 var = (invstd.pow(-2) - bn.eps) * (n / max(n - 1, 1))
                 bn.running_mean.mul_(1 - m).add_(mean, alpha=m)
                 bn.running_var.mul_(1 - m).add_(var, alpha=m)
-        return cfm.linear(z, P[20].view(d, d), P[21], x, p, s, 1.0, f32)
+        return cfm.linear(z, wp2, bp2, x, p, s, 1.0, f32)
 
-    x1 = ffn(x, 0, seed)
-    if layer.convolution_first:
-        x3 = mha(conv(x1, seed + 10), seed + 20)
-    else:
-        x3 = conv(mha(x1, seed + 20), seed + 10)
-    x4 = ffn(x3, 22, seed + 30)
-    return cfm.layer_norm(x4, P[28], P[29], _EPS, f32)[0]
+    run = {"ffn": ffn, "mha": mha, "conv": conv}
+    for m in module_order(layer.convolution_first):
+        x = run[m.kind](x, m.slots, seed + m.seed)
+    return cfm.layer_norm(x, *wb(FINAL_LN), _EPS, f32)[0]
