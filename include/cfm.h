@@ -915,6 +915,33 @@ int cfm_ctc_beam_decode_lm(const float* logits, long sb, long st, const int32_t*
                            const cfm_ngram_lm* lm, int32_t* bp_parent, int32_t* bp_token, int32_t* tokens,
                            int32_t* out_len, float* score, void* ws, void* stream);
 
+/* CTC forced alignment: the best single alignment (Viterbi path) of a GIVEN transcript, where the loss sums all of
+ * them and the decoders search for the transcript.  The reference has no counterpart; the surface is modelled on
+ * torchaudio.functional.forced_align, batched and with per-token spans.  logits, sb / st, targets / ldt / tgt_off,
+ * in_len, tgt_len, Smax and blank as cfm_ctc_loss_fwd (logits or log-probabilities: log-softmax is applied; lengths
+ * and labels are device data, clamped, never read back; 2 * Smax + 1 <= 1024, CFM_ERR_UNSUPPORTED above 511 labels;
+ * targets may be NULL when Smax == 0).  Over the states blank, l1, blank, l2, ..., blank (S_b = 2 L_b + 1):
+ *   v[t, s] = lpe[t, s] + max(v[t-1, s], v[t-1, s-1], v[t-1, s-2] if s is a label other than label s-2),
+ *   v[0, 0] = lpe[0, 0], v[0, 1] = lpe[0, 1];  equal predecessors prefer stay, then s-1, then s-2, and at the last
+ *   frame the final blank S_b - 1 wins a tie against S_b - 2 (the tie rule is part of the contract).
+ * Outputs, caller-allocated:
+ *   alignments (B, T) int32  the label (blank included) of each frame t < in_len[b]; -1 beyond
+ *   scores (B, T) fp32       its log-probability; 0 beyond
+ *   score (B) fp32           the path's log-probability (natural log)
+ *   starts, ends (B, Smax) int32, token_scores (B, Smax) fp32 (all three or none, NULL): per target position
+ *     u < L_b the first frame of its label, one past the last, and the sum of `scores` over the span in frame order
+ *     (one thread, no atomics); -1 / -1 / 0 for u >= L_b.
+ * An utterance with in_len[b] < L_b + (adjacent equal labels) has no alignment (so has in_len 0 with L_b > 0, and
+ * a best path whose score is not finite): score -inf, alignments -1, scores 0, spans -1 / -1 / 0.  in_len 0 with
+ * L_b 0: score 0.  L_b 0: every frame blank.  ws: cfm_ctc_align_ws_bytes(B, T, Smax).  Three launches (emissions,
+ * recursion, backtrace), no host synchronisation (graph-capturable), no wait on another wave's progress anywhere;
+ * results are bit-identical from run to run. */
+size_t cfm_ctc_align_ws_bytes(int B, int T, int Smax);
+int cfm_ctc_forced_align(const float* logits, long sb, long st, const int32_t* targets, int ldt,
+                         const int32_t* tgt_off, const int32_t* in_len, const int32_t* tgt_len, int B, int T, int V,
+                         int Smax, int blank, int32_t* alignments, float* scores, float* score, int32_t* starts,
+                         int32_t* ends, float* token_scores, void* ws, void* stream);
+
 /* BiLSTM decoder recurrence: replaces the cuDNN/MIOpen recurrence of the
  * reference's nn.LSTM (asrnn.py:38 construct, :252 call on the 2-D encoder output = ONE unbatched
  * sequence of L = B*T_enc steps).  Gate order i, f, g, o (torch).  One cooperative launch per pass;

@@ -323,6 +323,10 @@ _SIGS = {
     "cfm_ctc_beam_decode_lm": (c_int, [c_void_p, c_long, c_long, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                        c_int, c_int, c_float, c_float, c_int, ctypes.POINTER(NGramLMDesc), c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cfm_ctc_align_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "cfm_ctc_forced_align": (c_int, [c_void_p, c_long, c_long, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                     c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p]),
     "cfm_lstm_ws_bytes": (c_size_t, [c_int, c_int]),   # (H, ndir)
     "cfm_lstm_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                              c_void_p]),

@@ -12,11 +12,17 @@
                        (myvocab.py:211-231: <pad>/<blank> dropped, no repeat collapse by default).
   beam_search_decode   CTC prefix beam search: the alternative to that argmax (modelled on torchaudio's CUDA
                        CTC decoder), alone or with a back-off n-gram language model (lm.NGramLM) fused in.
+  forced_align         the best single alignment (Viterbi path) of a GIVEN transcript: per-frame labels and scores,
+                       per-token frame spans and the path's score (modelled on torchaudio.functional.forced_align,
+                       batched).  No reference counterpart; the Runner uses it for word spans (Runner.align) and for
+                       the confidence filter of the pseudo-label pass (hp.nst_min_confidence).
 
 Everything is stream-ordered with no host synchronisation when targets are padded (B, S) and the
 lengths are device tensors, so a whole training step can be captured into one HIP graph.
 """
 from __future__ import annotations
+
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -250,3 +256,66 @@ def beam_search_decode(logits, lengths=None, beam_size=16, blank=0, pad=-1, nbes
     if return_trace:
         return tokens, lens, scores, (bp_parent, bp_token)
     return tokens, lens, scores
+
+
+ForcedAlignment = namedtuple("ForcedAlignment", "alignments scores score starts ends token_scores")
+ALIGN_MAX_LABELS = 511
+
+
+def forced_align(logits, targets, input_lengths=None, target_lengths=None, blank=0, batch_first=True):
+    """CTC forced alignment on the device (cfm_ctc_forced_align): the best single alignment of each utterance's
+    transcript.  logits (B, T, V) fp32 CUDA (or (T, B, V) with batch_first=False), raw or log-probabilities (the
+    log-softmax is fused and idempotent); targets padded (B, Smax) or 1-D concatenated, as for ctc_loss;
+    input_lengths None: every utterance is T long; target_lengths None (padded targets only): Smax.  At most 511
+    labels per utterance.  Host-side lengths are validated as for the loss, and host-side targets that contain
+    `blank` within their (host-side) lengths raise ValueError; device lengths and targets are not read back -- the
+    kernels clamp them.  Returns the named tuple
+      alignments (B, T) int32     the label of each frame (blank included); -1 at and beyond the utterance's length
+      scores (B, T) fp32          the frame's log-probability of that label; 0 beyond
+      score (B,) fp32             the alignment's log-probability, the sum of its scores
+      starts, ends (B, Smax) int32, token_scores (B, Smax) fp32   per target position: the first frame of its label,
+                                  one past the last, the sum of `scores` over the span; -1 / -1 / 0 past the length
+    Frames are rows of `logits` (encoder output frames).
+    Tie rule: among equally good predecessors the path prefers to stay in its state, then to come from the state
+    before, then to skip the blank; at the last frame the final blank wins a tie against the last label.
+    Infeasible utterances (fewer frames than labels plus adjacent equal label pairs, so also no frames but labels;
+    or a best path whose score is not finite): score -inf, alignments -1, scores 0, spans -1 / -1 / 0.  No frames
+    and no labels: score 0.  No labels: every frame blank."""
+    if not torch.is_tensor(logits) or not logits.is_cuda or logits.dtype != torch.float32:
+        raise RuntimeError("forced_align runs on libcfm: fp32 CUDA logits required")
+    if logits.dim() != 3:
+        raise ValueError("logits must be (B, T, V), or (T, B, V) with batch_first=False")
+    x = logits if logits.stride(-1) == 1 else logits.contiguous()
+    B = x.shape[0] if batch_first else x.shape[1]
+    T = x.shape[1] if batch_first else x.shape[0]
+    blank = int(blank)
+    _check_blank(blank, x.shape[-1])
+    if not torch.is_tensor(targets):
+        targets = torch.tensor(targets, dtype=torch.int64)
+    if targets.dim() == 2 and targets.shape[0] != B:
+        raise ValueError(f"expected targets for {B} utterances, got {targets.shape[0]}")
+    if input_lengths is None:
+        input_lengths = torch.full((B,), T, dtype=torch.int32, device=x.device)
+    if target_lengths is None:
+        if targets.dim() != 2:
+            raise ValueError("target_lengths may be omitted only with padded (B, Smax) targets")
+        target_lengths = torch.full((B,), targets.shape[1], dtype=torch.int32, device=x.device)
+        host_tl = [targets.shape[1]] * B
+    elif torch.is_tensor(target_lengths):
+        host_tl = None if target_lengths.is_cuda else target_lengths.tolist()
+    else:
+        host_tl = list(target_lengths)
+    il = _lengths(input_lengths, B, x.device, T, "input_lengths")
+    tl = _lengths(target_lengths, B, x.device, targets.shape[1] if targets.dim() == 2 else None, "target_lengths")
+    if not targets.is_cuda and host_tl is not None:
+        rows = targets.tolist()
+        if targets.dim() == 2:
+            bad = any(blank in r[:n] for r, n in zip(rows, host_tl))
+        else:
+            bad = blank in rows[:sum(host_tl)]
+        if bad:
+            raise ValueError(f"targets must not contain the blank index {blank}")
+    tg, ldt, off, smax = _prep_targets(targets, tl, B, x.device)
+    if smax > ALIGN_MAX_LABELS:
+        raise ValueError(f"forced_align takes at most {ALIGN_MAX_LABELS} labels per utterance, got {smax}")
+    return ForcedAlignment(*ops.ctc_forced_align(x, tg, ldt, off, il, tl, smax, blank, batch_first))

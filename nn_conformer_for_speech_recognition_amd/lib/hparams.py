@@ -19,6 +19,10 @@ MI355X build (documented in DESIGN.md):
   lm_weight, word_bonus  float             lm_weight, plus word_bonus per emitted token; token_beam: the tokens each
   token_beam             int               entry is extended by (0: the default rule).  Not the reference's hp.lm
                                            flag, which means "train the transformer LM"
+  nst_min_confidence     float | None      None: every pseudo-label is kept (the reference).  A number: the label
+                                           pass force-aligns each beam hypothesis and drops the labels whose best
+                                           alignment has a mean per-frame log-probability below it
+                                           (set_nst_min_confidence; needs beam_size > 0)
 """
 from __future__ import annotations
 
@@ -64,7 +68,7 @@ _NST_LM = dict(nst=True, lm=False, train_lm=False, ft_lr=3e-6, ft_epochs=3, ft_t
                lm_max_len=20, just_nst=True)
 _BUILD = dict(compute_dtype="bf16", frontend_proj="utterance", pos_enc="none", use_group_norm=False,
               specaug_ref_noop_masks=False, dp_world_size=1, layer_norm_eps=1e-5, bn_eps=1e-5, bn_momentum=0.1, beam_size=0,
-              decoder_lm=None, lm_weight=0.0, word_bonus=0.0, token_beam=0)
+              decoder_lm=None, lm_weight=0.0, word_bonus=0.0, token_beam=0, nst_min_confidence=None)
 
 
 class HParams:
@@ -123,6 +127,13 @@ class HParams:
         lm=None clears it."""
         self.decoder_lm = lm
         self.lm_weight, self.word_bonus, self.token_beam = float(lm_weight), float(word_bonus), int(token_beam)
+
+    def set_nst_min_confidence(self, v):
+        """Confidence filter of the noisy-student label pass: a pseudo-label is kept when score / max(T_b, 1) >= v,
+        with score the log-probability of the best CTC alignment of the label (ctc.forced_align) and T_b the
+        utterance's encoder frames; a dropped label is None and MelDataset.mix_datasets leaves its clip out.
+        Needs beam_size > 0.  None (the default) switches the filter off."""
+        self.nst_min_confidence = None if v is None else float(v)
 
     def set_ntokens(self, ntokens):
         self.ntokens = ntokens

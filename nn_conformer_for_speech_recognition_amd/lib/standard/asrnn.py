@@ -22,7 +22,8 @@ import torch.nn as nn
 
 from ... import specaugment as _sa
 from ...conformer import Conformer
-from ...ctc import beam_search_decode as _beam_search_decode, greedy_decode as _greedy_decode
+from ...ctc import beam_search_decode as _beam_search_decode, forced_align as _forced_align, \
+    greedy_decode as _greedy_decode
 from ...frontend import frame_frontend as _frame_frontend, linear as _linear, projection_block as _projection_block
 from ...lstm import LSTM
 from ..convsubsampling import ConvSubSampling
@@ -93,6 +94,14 @@ class ASRNN(nn.Module):
                                          blank=int(self.hp.blank_idx), pad=pad, nbest=1, lm=lm, lm_weight=lm_weight,
                                          word_bonus=word_bonus, token_beam=token_beam)
         return toks[:, 0], n[:, 0]
+
+    def align(self, x, targets, lengths=None, target_lengths=None):
+        """CTC forced alignment of `targets` against the model's output x (B, T, V) (cfm_ctc_forced_align, blank =
+        hp.blank_idx): ctc.forced_align's named tuple -- per-frame labels and scores, the alignment's score and the
+        per-token spans, in encoder output frames.  lengths: the valid frames per utterance (None: all);
+        target_lengths: the labels per utterance (None: every column of padded targets)."""
+        return _forced_align(x.float() if x.dtype != torch.float32 else x, targets, lengths, target_lengths,
+                             blank=int(self.hp.blank_idx))
 
     def conformer_blocks(self, x, lengths=None):
         """asrnn.py:60-71 (kept for API parity): x (B, T, d) through the Conformer layers in turn."""

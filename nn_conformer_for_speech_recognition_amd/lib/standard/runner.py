@@ -16,6 +16,11 @@ Same constructor, methods and control flow as the reference; what runs underneat
                with ctc.beam_search_decode (CTC prefix beam search on the device, best hypothesis, <pad> never
                emitted, the model's output lengths) instead of the argmax; with hp.decoder_lm (set_decoder_lm)
                an n-gram LM is fused into that search (hp.lm_weight, hp.word_bonus, hp.token_beam).
+  align        Runner.align: ctc.forced_align of every clip's transcript against the eval-mode forward -> per word
+               (word, start frame, end frame, score), in encoder output frames (no reference counterpart).
+  confidence   hp.nst_min_confidence (default None: off): generate_labels force-aligns each beam hypothesis against
+               the same logits and returns None for the labels whose mean per-frame log-probability along the best
+               alignment is below the threshold; MelDataset.mix_datasets leaves those clips out.
   WER          myvocab.wer (jiwer's sentence-list WER; jiwer is not in this image)
 
 Dropped (outside the hot path): tqdm colours, Evals plots (losses / WER are kept on
@@ -32,7 +37,7 @@ from statistics import mean
 import torch
 import torch.nn as nn
 
-from ...ctc import CTCLoss, beam_search_decode, greedy_decode
+from ...ctc import CTCLoss, beam_search_decode, forced_align, greedy_decode
 from ...optim import Adafactor
 from .myvocab import wer
 
@@ -90,9 +95,10 @@ class Runner:
                                   "path; for n-gram shallow fusion in the decoder see HParams.set_decoder_lm")
 
     # ----------------------------------------------------------------------------- train / test
-    def _beam_labels(self, voc, logits, lengths):
+    def _beam_labels(self, voc, logits, lengths, confidence=False):
         """hp.beam_size > 0: the best prefix-beam-search hypothesis per utterance as label strings (lengths: the
-        model's output lengths, padded / truncated to the batch; the kernel clamps them to [0, T])."""
+        model's output lengths, padded / truncated to the batch; the kernel clamps them to [0, T]).  confidence (the
+        pseudo-label pass) with hp.nst_min_confidence set: None in place of a label whose confidence is below it."""
         if lengths is not None:
             B = logits.shape[0]
             lengths = nn.functional.pad(lengths[:B], (0, max(0, B - lengths.shape[0])))
@@ -101,9 +107,26 @@ class Runner:
         if lm is not None:
             kw = dict(lm=lm, lm_weight=float(self.hp.lm_weight), word_bonus=float(self.hp.word_bonus),
                       token_beam=int(self.hp.token_beam) or None)
-        toks, cnt, _ = beam_search_decode(logits.float() if logits.dtype != torch.float32 else logits, lengths,
-                                          beam_size=int(self.hp.beam_size), blank=voc.blank_idx, pad=voc.pad_idx, **kw)
-        return voc.decode(toks[:, 0], cnt[:, 0])
+        logits = logits.float() if logits.dtype != torch.float32 else logits
+        toks, cnt, _ = beam_search_decode(logits, lengths, beam_size=int(self.hp.beam_size), blank=voc.blank_idx,
+                                          pad=voc.pad_idx, **kw)
+        labels = voc.decode(toks[:, 0], cnt[:, 0])
+        thr = getattr(self.hp, "nst_min_confidence", None)
+        if thr is None or not confidence:
+            return labels
+        conf = self._confidence(voc, logits, lengths, toks[:, 0], cnt[:, 0])
+        return [None if c < thr else lab for lab, c in zip(labels, conf)]
+
+    @staticmethod
+    def _confidence(voc, logits, lengths, toks, cnt):
+        """Mean per-frame log-probability of the best CTC alignment of each hypothesis (toks (B, T) int32 padded with
+        -1, cnt (B,)) on the logits it was decoded from: forced_align's score / max(T_b, 1), as a list of floats."""
+        B, T = logits.shape[:2]
+        smax = max(int(cnt.max().item()), 1)
+        frames = (torch.full((B,), T, device=logits.device, dtype=torch.int32) if lengths is None
+                  else lengths.to(torch.int32).clamp(0, T))
+        score = forced_align(logits, toks[:, :smax].clamp(min=0), frames, cnt, blank=voc.blank_idx).score
+        return (score / frames.clamp(min=1)).tolist()
 
     def _metric(self, dataset, logits, target, lengths=None):
         if getattr(self.hp, "beam_size", 0) > 0:
@@ -172,7 +195,12 @@ class Runner:
 
     # ----------------------------------------------------------------------------- NST labels
     def generate_labels(self, dataset):
-        """runner.py:253-281: pseudo-labels for every clip of dataset's 'pretrain' split, in order."""
+        """runner.py:253-281: pseudo-labels for every clip of dataset's 'pretrain' split, in order.  With
+        hp.nst_min_confidence set, a label whose confidence (Runner._confidence) is below it is None."""
+        if getattr(self.hp, "nst_min_confidence", None) is not None and getattr(self.hp, "beam_size", 0) <= 0:
+            raise ValueError("hp.nst_min_confidence needs hp.beam_size > 0: the greedy label path does not collapse "
+                             "repeated frames (Vocab.decode, the reference's rule), so its labels generally have no "
+                             "CTC alignment to take a confidence from")
         self.model.eval()
         n = ceil(len(dataset.idxes["pretrain"]) / self.hp.batch_size)
         voc = dataset.vocab
@@ -185,7 +213,7 @@ class Runner:
                 batch = dataset.get_batch(i, "pretrain")["input"]
                 logits, out_lens = self.model(batch["mels"], batch["tau"])
                 if getattr(self.hp, "beam_size", 0) > 0:
-                    mine[i] = self._beam_labels(voc, logits, out_lens)
+                    mine[i] = self._beam_labels(voc, logits, out_lens, confidence=True)
                     continue
                 # ASRNN.predict + Vocab.decode in one device pass: argmax, <pad>/<blank> removed, no collapse
                 _, toks, cnt = greedy_decode(logits, None, blank=voc.blank_idx, pad=voc.pad_idx, collapse=False)
@@ -200,6 +228,33 @@ class Runner:
         for i in range(n):
             targets += mine[i]
         return targets
+
+    # ----------------------------------------------------------------------------- forced alignment
+    def align(self, dataset, dataset_type="test"):
+        """Where each word of each clip's transcript lies: an eval-mode forward per batch (as test()), then
+        ctc.forced_align of the transcript against the logits.  Returns, per clip in dataset order, a list of
+        (word, start_frame, end_frame, token_score) over the clip's transcript: the word's label occupies the frames
+        [start_frame, end_frame) and token_score is the sum of its frames' log-probabilities.  Frames are encoder
+        output frames (rows of the model's output, after the convolutional subsampling), not seconds.  A clip whose
+        transcript cannot be aligned (fewer frames than labels plus repeated neighbours) gets -1, -1, 0.0 per word."""
+        self.model.eval()
+        n = ceil(len(dataset.idxes[dataset_type]) / self.hp.batch_size)
+        voc = dataset.vocab
+        out = []
+        with torch.no_grad():
+            for i in range(n):
+                batch = dataset.get_batch(i, dataset_type)
+                target, target_lens = batch["target"]["transcripts"], batch["target"]["lens"]
+                logits, output_lens = self.model(batch["input"]["mels"], batch["input"]["tau"])
+                output_lens = nn.functional.pad(output_lens, (0, self.hp.batch_size - output_lens.shape[0]))
+                output_lens = output_lens.clamp(min=0, max=logits.shape[1])
+                a = self.model.align(logits, target, output_lens, target_lens)
+                ids, lens = target.tolist(), target_lens.tolist()
+                starts, ends, tsc = a.starts.tolist(), a.ends.tolist(), a.token_scores.tolist()
+                for b in range(batch["unpadded_len"]):
+                    out.append([(voc.itos[ids[b][u]], starts[b][u], ends[b][u], tsc[b][u]) for u in range(lens[b])])
+        self._check_device_errors()
+        return out
 
     def _check_device_errors(self):
         """End-of-pass synchronising check of the BiLSTM recurrences' wait-limit flags: each forward only polls

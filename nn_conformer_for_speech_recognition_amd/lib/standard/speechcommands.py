@@ -11,7 +11,8 @@ synthetic arrays.  What the Runner's hot path depends on is kept:
                                     (B, max_target_len), target.lens, unpadded_len  (:176-198)
   shuffle(type)                     python random, in place (:156-165)
   mix_datasets(U, targets)          NST: labelled train set + U with generated labels (empty label ->
-                                    [0]), dropping labels longer than max_target_len (:211-226)
+                                    [0]), dropping labels longer than max_target_len (:211-226) and the
+                                    clips whose label is None (hp.nst_min_confidence)
 """
 from __future__ import annotations
 
@@ -83,10 +84,12 @@ class MelDataset:
 
     def mix_datasets(self, U, targets):
         """speechcommands.py:211-226: train + U's clips with the generated labels."""
-        enc = [self.vocab.parse(t) if len(t) > 0 else [0] for t in targets]
+        enc = [None if t is None else (self.vocab.parse(t) if len(t) > 0 else [0]) for t in targets]
         n = min(len(U.data["pretrain"]), len(enc))
         u = []
         for i in range(n):
+            if targets[i] is None:                       # dropped by the confidence filter (hp.nst_min_confidence)
+                continue
             if len(enc[i]) > self.max_target_len:
                 continue
             t = enc[i] + [self.vocab.pad_idx] * (self.max_target_len - len(enc[i]))

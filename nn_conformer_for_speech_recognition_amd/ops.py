@@ -1131,3 +1131,21 @@ def ctc_beam_decode_lm(x, lm_tables, lengths_i32=None, beam=16, token_beam=17, l
            ctypes.byref(desc), L.ptr(bp_parent), L.ptr(bp_token), L.ptr(tokens), L.ptr(out_len), L.ptr(score),
            L.ptr(ws), L.stream())
     return tokens, out_len, score, bp_parent, bp_token
+
+
+def ctc_forced_align(x, targets_i32, ldt, tgt_off, in_len_i32, tgt_len_i32, smax, blank, batch_first=True):
+    """CTC forced alignment (cfm_ctc_forced_align) -> alignments (B, T) int32, scores (B, T) fp32, score (B,) fp32,
+    starts / ends (B, smax) int32 and token_scores (B, smax) fp32."""
+    B, T, sb, st = _rows(x, batch_first)
+    dev = x.device
+    alignments = torch.empty(B, T, device=dev, dtype=torch.int32)
+    scores = torch.empty(B, T, device=dev, dtype=torch.float32)
+    score = torch.empty(B, device=dev, dtype=torch.float32)
+    starts = torch.empty(B, smax, device=dev, dtype=torch.int32)
+    ends = torch.empty(B, smax, device=dev, dtype=torch.int32)
+    token_scores = torch.empty(B, smax, device=dev, dtype=torch.float32)
+    ws = workspace(L.size_call("cfm_ctc_align_ws_bytes", B, T, int(smax)), dev)
+    L.call("cfm_ctc_forced_align", L.ptr(x), sb, st, L.ptr(targets_i32), ldt, L.ptr(tgt_off), L.ptr(in_len_i32),
+           L.ptr(tgt_len_i32), B, T, x.shape[-1], int(smax), int(blank), L.ptr(alignments), L.ptr(scores), L.ptr(score),
+           L.ptr(starts), L.ptr(ends), L.ptr(token_scores), L.ptr(ws), L.stream())
+    return alignments, scores, score, starts, ends, token_scores
