@@ -958,6 +958,37 @@ int cfm_lstm_fwd(const float* gx, const float* whh, float* y, float* gates, floa
 int cfm_lstm_bwd(const float* dy, const float* whh, const float* gates, const float* c, float* dg,
                  int L, int H, int ndir, void* ws, void* stream);
 
+/* Batched LSTM recurrence (csrc/lstm_batched.hip): B independent sequences of up to T steps side by side, the
+ * recurrence of nn.LSTM on a 3-D input with packed-sequence semantics.  Gate order, widths and limits are those of
+ * cfm_lstm_fwd (H % 8 == 0, H <= 1024, ndir 1 or 2); any B >= 1 and T >= 1.
+ *   Every per-step array has B*T rows, fp32: gx, gates, dg (., ndir*4H); y, c, hprev, dy (., ndir*H).  The row of
+ *   (b, t) is b*stride_b + t*stride_t: batch-major (B, T, .) is stride_b = T, stride_t = 1; time-major (T, B, .) is
+ *   stride_b = 1, stride_t = B (the strides must address exactly the B*T rows).
+ *   whh (ndir, 4H, H) as for cfm_lstm_fwd; whh_t (ndir, H, 4H): each direction's W_hh transposed (the backward
+ *   product then reads weight rows along its reduction, like the forward).  whh, whh_t, y and dg 16-B aligned.
+ *   lengths (B) int32 on the device, or NULL for all T; each entry is clamped to [0, T] by the kernels and never
+ *   read back.  Sequence b runs t = 0 .. len_b-1 (forward direction) and t = len_b-1 .. 0 (reverse direction: the
+ *   packed sequence reversed, not the padded buffer), both from a zero state.
+ *   hprev (may be NULL): the state that fed each step, h_{t-1} (forward half) / h_{t+1} (reverse half), 0 at a
+ *   sequence's first step per direction -- the operand of the dW_hh GEMM, dW_hh[dir] = dg[:, dir]^T hprev[:, dir].
+ * Padding positions (t >= len_b): y = 0, hprev = 0 and dg = 0 are stored, exactly, in both directions; gates and c
+ * are left unwritten; gx, dy and the previous contents of any buffer are never read there (selects, no 0/1
+ * multiplications), so nothing at a valid position depends on a padding value.  len_b = 0: all padding.
+ * One plain kernel launch per time step, issued in a stream-ordered loop of T launches by the entry point, each
+ * covering all B sequences and both directions: no cooperative launch and no wait on another workgroup, hence no
+ * error flag to poll, and both calls are HIP-graph-capturable.  fp32 throughout, no atomics: two runs are
+ * bit-identical, and a sequence's results do not depend on its index in the batch.
+ * ws: cfm_lstm_batched_ws_bytes(B, T, H, ndir) bytes of device scratch for the backward, which carries the cell
+ * gradient dc_{t+-1} f_{t+-1} per (b, unit) there between its launches (B*ndir*H floats, no initialisation needed);
+ * the forward uses none (ws may be NULL). */
+size_t cfm_lstm_batched_ws_bytes(int B, int T, int H, int ndir);
+int cfm_lstm_batched_fwd(const float* gx, const float* whh, const int32_t* lengths, float* y, float* gates, float* c,
+                         float* hprev, int B, int T, long stride_b, long stride_t, int H, int ndir, void* ws,
+                         void* stream);
+int cfm_lstm_batched_bwd(const float* dy, const float* whh_t, const float* gates, const float* c,
+                         const int32_t* lengths, float* dg, int B, int T, long stride_b, long stride_t, int H,
+                         int ndir, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

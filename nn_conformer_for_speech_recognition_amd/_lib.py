@@ -332,6 +332,13 @@ _SIGS = {
                              c_void_p]),
     "cfm_lstm_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                              c_void_p]),
+    "cfm_lstm_batched_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),   # (B, T, H, ndir)
+    # (gx, whh, lengths, y, gates, c, hprev, B, T, stride_b, stride_t, H, ndir, ws, stream)
+    "cfm_lstm_batched_fwd": (c_int, [c_void_p] * 7 + [c_int, c_int, c_long, c_long, c_int, c_int, c_void_p,
+                                                      c_void_p]),
+    # (dy, whh_t, gates, c, lengths, dg, B, T, stride_b, stride_t, H, ndir, ws, stream)
+    "cfm_lstm_batched_bwd": (c_int, [c_void_p] * 6 + [c_int, c_int, c_long, c_long, c_int, c_int, c_void_p,
+                                                      c_void_p]),
     "cfm_ffold_geometry": (c_int, [c_void_p]),
     "cfm_ffold_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "cfm_ffold_compose": (c_int, [c_void_p] * 11),

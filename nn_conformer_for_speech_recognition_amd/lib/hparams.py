@@ -23,6 +23,10 @@ MI355X build (documented in DESIGN.md):
                                            pass force-aligns each beam hypothesis and drops the labels whose best
                                            alignment has a mean per-frame log-probability below it
                                            (set_nst_min_confidence; needs beam_size > 0)
+  decoder_batched        bool              False: the reference's decoder call, one LSTM sequence over the whole
+                                           batch (asrnn.py:252).  True: one sequence per utterance, bounded by the
+                                           model's output lengths (set_decoder_batched); same state dict, but a
+                                           model trained in one mode sees different decoder states in the other
 """
 from __future__ import annotations
 
@@ -68,7 +72,8 @@ _NST_LM = dict(nst=True, lm=False, train_lm=False, ft_lr=3e-6, ft_epochs=3, ft_t
                lm_max_len=20, just_nst=True)
 _BUILD = dict(compute_dtype="bf16", frontend_proj="utterance", pos_enc="none", use_group_norm=False,
               specaug_ref_noop_masks=False, dp_world_size=1, layer_norm_eps=1e-5, bn_eps=1e-5, bn_momentum=0.1, beam_size=0,
-              decoder_lm=None, lm_weight=0.0, word_bonus=0.0, token_beam=0, nst_min_confidence=None)
+              decoder_lm=None, lm_weight=0.0, word_bonus=0.0, token_beam=0, nst_min_confidence=None,
+              decoder_batched=False)
 
 
 class HParams:
@@ -134,6 +139,12 @@ class HParams:
         utterance's encoder frames; a dropped label is None and MelDataset.mix_datasets leaves its clip out.
         Needs beam_size > 0.  None (the default) switches the filter off."""
         self.nst_min_confidence = None if v is None else float(v)
+
+    def set_decoder_batched(self, flag):
+        """True: ASRNN runs the BiLSTM decoder per utterance (lstm.LSTM on the 3-D encoder output with the
+        Conformer's frame counts as lengths) instead of as one sequence over the batch.  A model option like
+        use_group_norm: the parameters are the same, the decoder states are not."""
+        self.decoder_batched = bool(flag)
 
     def set_ntokens(self, ntokens):
         self.ntokens = ntokens

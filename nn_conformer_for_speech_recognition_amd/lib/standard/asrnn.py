@@ -66,7 +66,7 @@ class ASRNN(nn.Module):
         dec_layers = hp.standard_decoder_layers
         self.lstm = LSTM(hp.projection_out_size, hp.standard_decoder_nodes,
                             bidirectional=hp.standard_decoder_bidirectional, num_layers=dec_layers,
-                            dropout=hp.dropout if dec_layers > 1 else 0.0)
+                            dropout=hp.dropout if dec_layers > 1 else 0.0, batch_first=True)
         self.dropout = nn.Dropout(hp.dropout)
         dec_out = hp.standard_decoder_nodes * (2 if hp.standard_decoder_bidirectional else 1)
         self.final_fc = nn.Linear(dec_out, hp.ntokens)
@@ -190,12 +190,34 @@ class ASRNN(nn.Module):
         raise NotImplementedError("ASRNN.decoder is dead code in the reference (asrnn.py:223-236 uses "
                                   "undefined decoder_fc/relu)")
 
+    def decoder_lengths(self, output_lens, B, T_enc):
+        """The frames per utterance the per-utterance decoder (hp.decoder_batched) runs over: the frame counts the
+        Conformer itself used -- the encoder's output lengths, with the frame front-end's clamp(min=1) (encoder()
+        passes lens.clamp(min=1) to the Conformer and returns lens unclamped), padded with zeros to B (the
+        utterance front-end drops empty clips) and clamped to [0, T_enc].  (B,) int32 on the device, no host read."""
+        lens = output_lens
+        if self.frontend_proj == "frame":
+            lens = lens.clamp(min=1)
+        lens = nn.functional.pad(lens, (0, B - lens.shape[0]))
+        return lens.clamp(0, T_enc).to(torch.int32)
+
     def forward(self, x, input_lens, SpecAugment=False, lm=None, finetuning=False):
-        """asrnn.py:237-259: (B, F, T) mels -> log-probs (B, T_enc, ntokens), output lengths."""
+        """asrnn.py:237-259: (B, F, T) mels -> log-probs (B, T_enc, ntokens), output lengths.
+
+        hp.decoder_batched: the BiLSTM decoder gets the encoder output as a (B, T_enc, .) view and
+        decoder_lengths() as lengths, so every utterance is a sequence of its own from a zero state (its output
+        is 0 at its padding frames) instead of one link of a B*T_enc-step chain.  Everything after the LSTM is
+        unchanged, and so is the state dict; a checkpoint trained in one mode sees different decoder states in the
+        other (a model option like use_group_norm)."""
         B = x.shape[0]
         x = x.unsqueeze(1)
         x, output_lens = self.encoder(x, input_lens, SpecAugment, finetuning=finetuning)
-        x = self.lstm(x)[0]
+        if getattr(self.hp, "decoder_batched", False):
+            T_enc = x.shape[0] // B
+            lens = self.decoder_lengths(output_lens.to(x.device), B, T_enc)
+            x = self.lstm(x.view(B, T_enc, x.shape[1]), lengths=lens)[0].view(B * T_enc, -1)
+        else:
+            x = self.lstm(x)[0]
         x = self.dropout(x)
         x = self.final_fc(x)
         x = x.view((B, x.shape[0] // B, self.hp.ntokens))

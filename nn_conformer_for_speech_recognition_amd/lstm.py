@@ -14,8 +14,14 @@ reverse-time recurrence (cfm_lstm_bwd) produces the pre-activation gate gradient
 dW_ih, dW_hh (time-shifted views of dG and y, no copies) and the bias gradient are cfm_gemm / cfm_colsum.
 Everything computes in fp32, like the reference.
 
-Not supported (raise): batched 3-D input, an initial state hx (the reference passes neither).  c_n is
-returned without a gradient path (the reference discards the state tuple).
+Batched 3-D input (T, B, In) / (B, T, In) with `lengths=` runs B independent sequences side by side with
+packed-sequence semantics (cfm_lstm_batched_fwd / _bwd, csrc/lstm_batched.hip: one plain launch per time step
+over all sequences and both directions, no waits, graph-capturable, no error flag).  There dW_hh is one GEMM per
+direction against the predecessor states `hprev` the forward stores (zero at every sequence's first step and at
+padding), since a row-shifted view of y would cross utterance boundaries.
+
+Not supported (raise): an initial state hx, proj_size, a PackedSequence input (3-D input with lengths= is the
+supported form).  c_n is returned without a gradient path (the reference discards the state tuple).
 """
 from __future__ import annotations
 
@@ -131,14 +137,59 @@ class _LSTMLayer(torch.autograd.Function):
         return dx, dw_ih, dw_hh, db, None, None
 
 
+class _LSTMBatchedLayer(torch.autograd.Function):
+    """One (bi)directional layer over B sequences: x (B*T, In) fp32 with the row of (b, t) at b*sb + t*st;
+    lens: (B,) int32 device tensor or None (all T)."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, bias, lens, H, ndir, B, T, sb, st):
+        rows, dev = x.shape[0], x.device
+        gx = ops.linear(x, w_ih, bias=bias)                        # (B*T, ndir*4H)
+        y = torch.empty(rows, ndir * H, device=dev, dtype=torch.float32)
+        gates = torch.empty(rows, ndir * 4 * H, device=dev, dtype=torch.float32)
+        c = torch.empty(rows, ndir * H, device=dev, dtype=torch.float32)
+        hprev = torch.empty_like(y) if any(ctx.needs_input_grad) else None      # only the backward reads it
+        L.call("cfm_lstm_batched_fwd", L.ptr(gx), L.ptr(w_hh), L.ptr(lens), L.ptr(y), L.ptr(gates), L.ptr(c),
+               L.ptr(hprev), B, T, sb, st, H, ndir, None, L.stream())
+        ctx.save_for_backward(x, w_ih, w_hh, gates, c, hprev, lens)
+        ctx.geo = (H, ndir, B, T, sb, st)
+        ctx.mark_non_differentiable(c)
+        return y, c
+
+    @staticmethod
+    def backward(ctx, dy, _dc):
+        x, w_ih, w_hh, gates, c, hprev, lens = ctx.saved_tensors
+        H, ndir, B, T, sb, st = ctx.geo
+        rows, H4 = x.shape[0], 4 * H
+        dy = dy.float().contiguous()
+        dg = torch.empty(rows, ndir * H4, device=x.device, dtype=torch.float32)
+        ws = torch.empty(max(L.size_call("cfm_lstm_batched_ws_bytes", B, T, H, ndir) // 4, 1), device=x.device,
+                         dtype=torch.float32)
+        whh_t = w_hh.view(ndir, H4, H).transpose(1, 2).contiguous()
+        L.call("cfm_lstm_batched_bwd", L.ptr(dy), L.ptr(whh_t), L.ptr(gates), L.ptr(c), L.ptr(lens), L.ptr(dg), B, T,
+               sb, st, H, ndir, L.ptr(ws), L.stream())
+        # dg is exactly 0 at padding, so the GEMMs and column sums over all B*T rows are the packed ones
+        dx = ops.linear_dgrad(dg, w_ih) if ctx.needs_input_grad[0] else None
+        dw_ih = ops.linear_wgrad(dg, x)
+        db = ops.colsum(dg)
+        dw_hh = torch.zeros(ndir * H4, H, device=x.device, dtype=torch.float32)
+        if T > 1:                                                   # T == 1: every step is a first step, hprev = 0
+            ldg, ldy = ndir * H4, ndir * H
+            for d in range(ndir):
+                _wgrad_strided(dg[:, d * H4:], ldg, hprev[:, d * H:], ldy, H4, H, rows, dw_hh[d * H4:(d + 1) * H4])
+        return (dx, dw_ih, dw_hh, db) + (None,) * 7
+
+
 class LSTM(nn.Module):
-    """torch.nn.LSTM surface (unbatched 2-D input, zero initial state) on the libcfm recurrence."""
+    """torch.nn.LSTM surface (zero initial state) on the libcfm recurrences: unbatched 2-D input as one sequence,
+    or 3-D input with `lengths=` as B independent sequences."""
 
     def __init__(self, input_size, hidden_size, num_layers=1, bias=True, batch_first=False, dropout=0.0,
                  bidirectional=False, proj_size=0, device=None, dtype=None):
         super().__init__()
         if proj_size:
-            raise NotImplementedError("LSTM: proj_size is not supported")
+            raise NotImplementedError("LSTM: proj_size is not supported (2-D input, or 3-D input with lengths=, "
+                                      "on the plain cell, is the supported form)")
         if hidden_size % 8 or hidden_size > 1024:
             raise ValueError("LSTM: hidden_size must be a multiple of 8 and <= 1024 (cfm_lstm_fwd)")
         self.input_size, self.hidden_size, self.num_layers = input_size, hidden_size, num_layers
@@ -165,28 +216,48 @@ class LSTM(nn.Module):
     def _sfx(self):
         return [""] + (["_reverse"] if self.bidirectional else [])
 
-    def forward(self, input, hx=None):
-        """Wait-limit failures of the recurrence kernels are reported WITHOUT a host sync: this call raises for a
-        failure of an earlier pass whose flag copy has completed (typically one forward late), so the failing
+    def _layer_params(self, layer, device):
+        H, ndir = self.hidden_size, 2 if self.bidirectional else 1
+        sf = self._sfx()
+        w_ih = torch.cat([getattr(self, f"weight_ih_l{layer}{s}") for s in sf]).float().contiguous()
+        w_hh = torch.cat([getattr(self, f"weight_hh_l{layer}{s}") for s in sf]).float().contiguous()
+        if self.bias:
+            b = torch.cat([getattr(self, f"bias_ih_l{layer}{s}") + getattr(self, f"bias_hh_l{layer}{s}")
+                           for s in sf]).float().contiguous()
+        else:
+            b = torch.zeros(ndir * 4 * H, device=device, dtype=torch.float32)
+        return w_ih, w_hh, b
+
+    def forward(self, input, hx=None, lengths=None):
+        """2-D input (L, In): one unbatched sequence, the reference's call.  3-D input (T, B, In), or (B, T, In)
+        with batch_first: B independent sequences (_forward_batched); lengths: None (all T) or (B,) valid steps
+        as a list, a CPU tensor (both checked for count and sign) or a device tensor (checked for count only and
+        never read back: the kernels clamp it to [0, T]).
+
+        Wait-limit failures of the unbatched recurrence kernels are reported WITHOUT a host sync: this call raises
+        for a failure of an earlier pass whose flag copy has completed (typically one forward late), so the failing
         pass's outputs are already consumed.  Call LSTM.check_errors() at the end of a pass (Runner does, after
-        every epoch / test / label pass) for a synchronising check of everything launched so far."""
+        every epoch / test / label pass) for a synchronising check of everything launched so far.  The batched
+        recurrence has no waits and no flag."""
         if hx is not None:
-            raise NotImplementedError("LSTM: an initial state hx is not supported (the reference passes none)")
+            raise NotImplementedError("LSTM: an initial state hx is not supported (the reference passes none); "
+                                      "3-D input with lengths= is the supported batched form")
+        if isinstance(input, nn.utils.rnn.PackedSequence):
+            raise NotImplementedError("LSTM: a PackedSequence input is not supported; pass the padded 3-D input "
+                                      "with lengths=")
+        if input.dim() == 3:
+            return self._forward_batched(input, lengths)
         if input.dim() != 2:
-            raise NotImplementedError("LSTM: only the unbatched 2-D (L, input_size) form (asrnn.py:252) is supported")
+            raise NotImplementedError("LSTM: input must be 2-D (L, input_size), the unbatched form of asrnn.py:252, "
+                                      "or 3-D with lengths=")
+        if lengths is not None:
+            raise ValueError("LSTM: lengths= goes with 3-D input; a 2-D input is one unbatched sequence")
         H, ndir = self.hidden_size, 2 if self.bidirectional else 1
         ERRORS.poll(input.device)            # earlier passes' wait-limit flags (no host sync)
         x = input.float().contiguous()
         hn, cn = [], []
         for layer in range(self.num_layers):
-            sf = self._sfx()
-            w_ih = torch.cat([getattr(self, f"weight_ih_l{layer}{s}") for s in sf]).float().contiguous()
-            w_hh = torch.cat([getattr(self, f"weight_hh_l{layer}{s}") for s in sf]).float().contiguous()
-            if self.bias:
-                b = torch.cat([getattr(self, f"bias_ih_l{layer}{s}") + getattr(self, f"bias_hh_l{layer}{s}")
-                               for s in sf]).float().contiguous()
-            else:
-                b = torch.zeros(ndir * 4 * H, device=x.device, dtype=torch.float32)
+            w_ih, w_hh, b = self._layer_params(layer, x.device)
             y, c = _LSTMLayer.apply(x, w_ih, w_hh, b, H, ndir)
             hn.append(y[-1, :H])
             cn.append(c[-1, :H])
@@ -197,6 +268,68 @@ class LSTM(nn.Module):
             if layer < self.num_layers - 1 and self.dropout > 0 and self.training:
                 x = F.dropout(x, self.dropout, True)
         out = x.to(input.dtype) if input.dtype != torch.float32 else x
+        return out, (torch.stack(hn), torch.stack(cn))
+
+    def _forward_batched(self, input, lengths):
+        """torch's batched shapes: output (T, B, ndir*H) / (B, T, ndir*H) with zeros at padding (what
+        pad_packed_sequence(total_length=T) gives); h_n, c_n (num_layers*ndir, B, H) at each sequence's own last
+        step (t = len_b-1 forward, t = 0 reverse; zeros for len_b = 0), gathered with device index ops.  h_n
+        carries gradient through the output, c_n does not."""
+        H, ndir = self.hidden_size, 2 if self.bidirectional else 1
+        if self.batch_first:
+            B, T = input.shape[0], input.shape[1]
+        else:
+            T, B = input.shape[0], input.shape[1]
+        dev = input.device
+        lens = None
+        if lengths is not None:
+            if torch.is_tensor(lengths) and lengths.is_cuda:
+                if lengths.dim() != 1 or lengths.shape[0] != B:
+                    raise ValueError(f"LSTM: lengths must hold one entry per sequence ({B}), got {tuple(lengths.shape)}")
+                lens = lengths.to(torch.int32).contiguous()
+            else:
+                host = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+                if len(host) != B:
+                    raise ValueError(f"LSTM: lengths must hold one entry per sequence ({B}), got {len(host)}")
+                if any(v < 0 for v in host):
+                    raise ValueError("LSTM: lengths must not be negative")
+                lens = torch.tensor(host, dtype=torch.int32).to(dev) if B * T else None
+        nstate = self.num_layers * ndir
+        if B * T == 0:
+            shape = (B, T, ndir * H) if self.batch_first else (T, B, ndir * H)
+            return (torch.zeros(shape, device=dev, dtype=input.dtype),
+                    (torch.zeros(nstate, B, H, device=dev, dtype=torch.float32),
+                     torch.zeros(nstate, B, H, device=dev, dtype=torch.float32)))
+        sb, st = (T, 1) if self.batch_first else (1, B)
+        x = input.float().contiguous().view(B * T, input.shape[2])
+        if lens is not None:
+            lc = lens.clamp(0, T).long()
+            last = (lc - 1).clamp(min=0).view(B, 1, 1).expand(B, 1, H)
+            some = (lc > 0).view(B, 1)
+
+        def by_batch(a):                                   # (B*T, ndir*H) rows -> a (B, T, ndir*H) view
+            return a.view(B, T, ndir * H) if self.batch_first else a.view(T, B, ndir * H).transpose(0, 1)
+
+        hn, cn = [], []
+        for layer in range(self.num_layers):
+            w_ih, w_hh, b = self._layer_params(layer, dev)
+            y, c = _LSTMBatchedLayer.apply(x, w_ih, w_hh, b, lens, H, ndir, B, T, sb, st)
+            yb, cb = by_batch(y), by_batch(c)
+            if lens is None:
+                hn.append(yb[:, T - 1, :H])
+                cn.append(cb[:, T - 1, :H])
+            else:                                          # y is 0 at padding (so at t = 0 of an empty row); c is not
+                hn.append(yb[:, :, :H].gather(1, last).squeeze(1))
+                cn.append(torch.where(some, cb[:, :, :H].gather(1, last).squeeze(1), torch.zeros((), device=dev)))
+            if ndir == 2:
+                hn.append(yb[:, 0, H:])
+                cn.append(cb[:, 0, H:] if lens is None else
+                          torch.where(some, cb[:, 0, H:], torch.zeros((), device=dev)))
+            x = y
+            if layer < self.num_layers - 1 and self.dropout > 0 and self.training:
+                x = F.dropout(x, self.dropout, True)
+        out = x.view((B, T, ndir * H) if self.batch_first else (T, B, ndir * H))
+        out = out.to(input.dtype) if input.dtype != torch.float32 else out
         return out, (torch.stack(hn), torch.stack(cn))
 
     @staticmethod
