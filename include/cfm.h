@@ -942,6 +942,37 @@ int cfm_ctc_forced_align(const float* logits, long sb, long st, const int32_t* t
                          int Smax, int blank, int32_t* alignments, float* scores, float* score, int32_t* starts,
                          int32_t* ends, float* token_scores, void* ws, void* stream);
 
+/* Batched edit distance (Levenshtein) over token ids: the numerator of the word error rate -- the vocabulary's tokens
+ * are words -- in place of the host loop of jiwer's wer (reference runner.py:160,230), and the aligned pairs the
+ * reference's confusion matrix is built from (evals.py:64).  Pair p < P compares hypothesis row p (hyp + p * ldh,
+ * hyp_len[p] ids) with reference row p / group (ref + (p / group) * ldr, ref_len[p / group] ids); P == n_ref * group,
+ * group = N scores an n-best list against one transcript.  Lengths are device data, clamped on the device to
+ * [0, Rmax] and [0, Hmax] and never read back; ids past a row's length are never read into a result.
+ * Rmax <= ldr, Hmax <= ldh (CFM_ERR_SHAPE), both <= 1024 (CFM_ERR_UNSUPPORTED above); null, negative or
+ * P != n_ref * group arguments return CFM_ERR_ARG before any launch (ref / hyp may be NULL when Rmax / Hmax is 0).
+ * With r the reference (R ids) and h the hypothesis (H ids):
+ *   D[i][0] = i, D[0][j] = j,
+ *   D[i][j] = min(D[i-1][j-1] + (r[i-1] != h[j-1]), D[i-1][j] + 1, D[i][j-1] + 1)   for i, j >= 1,
+ *   dist[p] = D[R][H].
+ * Tie rule of the alignment (part of the contract): a cell's direction is the FIRST of diagonal (hit or
+ * substitution), up (deletion: a reference token without a partner), left (insertion) that attains the minimum;
+ * on the border i == 0 walks left and j == 0 walks up; the backtrace starts at (R, H).  From that one path:
+ *   counts (P, 4) int32 or NULL   hits, substitutions, deletions, insertions:
+ *                                 hits + subs + dels = R, hits + subs + ins = H, subs + dels + ins = dist
+ *   pair_ref, pair_hyp (P, ldp) int32 and n_pairs (P) int32 (all three or none, NULL), ldp >= Rmax + Hmax:
+ *                                 the path's pairs in forward order, -1 on the gap side, n_pairs[p] <= R + H of
+ *                                 them; entries past n_pairs[p] are -1 on both sides.
+ * counts == NULL and no pair outputs (want_ops = 0): one launch, no direction matrix is stored and ws may be NULL /
+ * 0 bytes (the training-metric path).  Otherwise ws holds the direction matrix, 2 bits per cell (16 anti-diagonal
+ * steps of a row per 32-bit word, rows padded by the 63-step skew of a 64-row strip), and a backtrace launch follows
+ * the recursion.  ws: cfm_edit_distance_ws_bytes(P, Rmax, Hmax, want_ops).  No host synchronisation
+ * (graph-capturable), one wave per pair and no wait on another wave's progress anywhere; results are bit-identical
+ * from run to run. */
+size_t cfm_edit_distance_ws_bytes(int P, int Rmax, int Hmax, int want_ops);
+int cfm_edit_distance(const int32_t* ref, int ldr, const int32_t* ref_len, int n_ref, const int32_t* hyp, int ldh,
+                      const int32_t* hyp_len, int P, int group, int Rmax, int Hmax, int32_t* dist, int32_t* counts,
+                      int32_t* pair_ref, int32_t* pair_hyp, int ldp, int32_t* n_pairs, void* ws, void* stream);
+
 /* BiLSTM decoder recurrence: replaces the cuDNN/MIOpen recurrence of the
  * reference's nn.LSTM (asrnn.py:38 construct, :252 call on the 2-D encoder output = ONE unbatched
  * sequence of L = B*T_enc steps).  Gate order i, f, g, o (torch).  One cooperative launch per pass;

@@ -327,6 +327,12 @@ _SIGS = {
     "cfm_ctc_forced_align": (c_int, [c_void_p, c_long, c_long, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                      c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p]),
+    "cfm_edit_distance_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),   # (P, Rmax, Hmax, want_ops)
+    # (ref, ldr, ref_len, n_ref, hyp, ldh, hyp_len, P, group, Rmax, Hmax, dist, counts, pair_ref, pair_hyp, ldp,
+    #  n_pairs, ws, stream)
+    "cfm_edit_distance": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                                  c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                  c_void_p]),
     "cfm_lstm_ws_bytes": (c_size_t, [c_int, c_int]),   # (H, ndir)
     "cfm_lstm_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                              c_void_p]),

@@ -16,6 +16,9 @@
                        per-token frame spans and the path's score (modelled on torchaudio.functional.forced_align,
                        batched).  No reference counterpart; the Runner uses it for word spans (Runner.align) and for
                        the confidence filter of the pseudo-label pass (hp.nst_min_confidence).
+  edit_distance        batched Levenshtein distance over token ids, optionally with the aligned pairs: the word error
+                       rate of runner.py:160,230 (jiwer's wer; the vocabulary's tokens are words) without the trip
+                       through strings on the host, and the pairs of the confusion matrix of evals.py:64.
 
 Everything is stream-ordered with no host synchronisation when targets are padded (B, S) and the
 lengths are device tensors, so a whole training step can be captured into one HIP graph.
@@ -319,3 +322,84 @@ def forced_align(logits, targets, input_lengths=None, target_lengths=None, blank
     if smax > ALIGN_MAX_LABELS:
         raise ValueError(f"forced_align takes at most {ALIGN_MAX_LABELS} labels per utterance, got {smax}")
     return ForcedAlignment(*ops.ctc_forced_align(x, tg, ldt, off, il, tl, smax, blank, batch_first))
+
+
+EditDistance = namedtuple("EditDistance", "distance ref_lengths counts pair_ref pair_hyp n_pairs")
+EDIT_MAX_LEN = 1024
+
+
+def _id_rows(t, what):
+    """(rows, ld): a 2-D id tensor as int32 with contiguous ids and a row stride ld >= its width (a view of `t` where
+    its dtype and strides allow, so strided batches are read in place)."""
+    if t.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{what} must be int32 or int64 ids, got {t.dtype}")
+    if t.dtype != torch.int32:
+        t = t.to(torch.int32)
+    n, w = t.shape
+    if n <= 1 or w == 0:
+        return t.contiguous(), w
+    if t.stride(1) != 1 or t.stride(0) < w:
+        t = t.contiguous()
+    return t, t.stride(0)
+
+
+def edit_distance(hyp, ref, hyp_lengths=None, ref_lengths=None, ops=False):
+    """Batched edit distance (Levenshtein) over token ids on the device (cfm_edit_distance).  The vocabulary's tokens
+    are words, so this is the word-level distance of jiwer's wer (runner.py:160,230).
+
+    hyp (B, Lh), or (B, N, Lh) for an n-best list per reference (group = N from the shape: results are (B, N));
+    ref (B, Lr); int32 or int64 CUDA tensors, rows may be strided (CPU tensors raise).  Lengths: device tensors, host
+    lists or None (the full row), hyp_lengths shaped like hyp without its last dimension; they are clamped to
+    [0, Lh] / [0, Lr] on the device and device lengths are never read back (no .item() / .tolist(): no host
+    synchronisation).  Lh, Lr <= 1024.  Ids past a row's length are never read into a result.
+
+    With r one reference (R ids) and h one hypothesis (H ids):
+      D[i][0] = i, D[0][j] = j,
+      D[i][j] = min(D[i-1][j-1] + (r[i-1] != h[j-1]), D[i-1][j] + 1, D[i][j-1] + 1)   for i, j >= 1,
+      distance = D[R][H].
+    ops=True adds ONE alignment, under this tie rule: a cell's direction is the first of diagonal (hit or
+    substitution), up (deletion: a reference token without a partner), left (insertion) that attains the minimum; on
+    the border i == 0 walks left and j == 0 walks up; the backtrace starts at (R, H).
+
+    Returns the named tuple (all int32)
+      distance (B,) / (B, N)
+      ref_lengths (B,)               the clamped reference lengths (the denominator of a WER)
+      counts (..., 4)                hits, substitutions, deletions, insertions of that path:
+                                     hits + subs + dels = R, hits + subs + ins = H, subs + dels + ins = distance
+      pair_ref, pair_hyp (..., Lr + Lh), n_pairs (...)   the path's pairs in forward order, -1 on the gap side,
+                                     n_pairs <= R + H of them; entries past n_pairs are -1 on both sides
+    counts, pair_ref, pair_hyp and n_pairs are None with ops=False (one launch, no direction matrix is stored)."""
+    want_ops = bool(ops)
+    from . import ops as _ops     # (the `ops` argument shadows the module here)
+    if not torch.is_tensor(hyp) or not torch.is_tensor(ref) or not hyp.is_cuda or not ref.is_cuda:
+        raise RuntimeError("edit_distance runs on libcfm: CUDA id tensors required")
+    if ref.dim() != 2 or hyp.dim() not in (2, 3):
+        raise ValueError("ref must be (B, Lr) and hyp (B, Lh) or (B, N, Lh)")
+    B, Lr = ref.shape
+    if hyp.shape[0] != B:
+        raise ValueError(f"expected hypotheses for {B} references, got {hyp.shape[0]}")
+    lead = tuple(hyp.shape[:-1])
+    group = hyp.shape[1] if hyp.dim() == 3 else 1
+    Lh = hyp.shape[-1]
+    if Lr > EDIT_MAX_LEN or Lh > EDIT_MAX_LEN:
+        raise ValueError(f"edit_distance takes at most {EDIT_MAX_LEN} ids per row, got Lr {Lr}, Lh {Lh}")
+    if hyp.dim() == 3 and group == 0:
+        raise ValueError("hyp (B, N, Lh) needs N >= 1")
+    P = B * group
+    dev = ref.device
+    r2, ldr = _id_rows(ref, "ref")
+    h2, ldh = _id_rows(hyp.reshape(P, Lh), "hyp")     # a view where the (B, N) strides allow
+    if ref_lengths is None:
+        rl = torch.full((B,), Lr, dtype=torch.int32, device=dev)
+    else:
+        rl = _lengths(ref_lengths, B, dev, None, "ref_lengths").reshape(-1).clamp(0, Lr)
+    if hyp_lengths is None:
+        hl = torch.full((P,), Lh, dtype=torch.int32, device=dev)
+    else:
+        hl = _lengths(hyp_lengths, P, dev, None, "hyp_lengths").reshape(-1)
+    dist, counts, pair_ref, pair_hyp, n_pairs = _ops.edit_distance(r2, ldr, rl, h2, ldh, hl, P, group, Lr, Lh,
+                                                                   want_ops)
+    if not want_ops:
+        return EditDistance(dist.view(lead), rl, None, None, None, None)
+    return EditDistance(dist.view(lead), rl, counts.view(lead + (4,)), pair_ref.view(lead + (Lr + Lh,)),
+                        pair_hyp.view(lead + (Lr + Lh,)), n_pairs.view(lead))

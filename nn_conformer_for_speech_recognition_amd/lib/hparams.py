@@ -27,6 +27,15 @@ MI355X build (documented in DESIGN.md):
                                            batch (asrnn.py:252).  True: one sequence per utterance, bounded by the
                                            model's output lengths (set_decoder_batched); same state dict, but a
                                            model trained in one mode sees different decoder states in the other
+  device_wer             bool              False: the reference's metric -- per batch, ids to the host, strings,
+                                           jiwer's wer over targets padded with '_' (runner.py:151-160), the mean
+                                           over the batches; one host synchronisation per step.  True
+                                           (set_device_wer): the Runner takes the word errors with ctc.edit_distance
+                                           on the device ids and accumulates errors, reference words and the loss in
+                                           device tensors read once per epoch / split.  The figure then DIFFERS from
+                                           the reference's: it is the corpus WER, 100 * sum(errors) / sum(reference
+                                           words) over the epoch or split (0.0 without words), not a mean of batch
+                                           figures over padded targets; the loss stays the mean of the per-step values
 """
 from __future__ import annotations
 
@@ -73,7 +82,7 @@ _NST_LM = dict(nst=True, lm=False, train_lm=False, ft_lr=3e-6, ft_epochs=3, ft_t
 _BUILD = dict(compute_dtype="bf16", frontend_proj="utterance", pos_enc="none", use_group_norm=False,
               specaug_ref_noop_masks=False, dp_world_size=1, layer_norm_eps=1e-5, bn_eps=1e-5, bn_momentum=0.1, beam_size=0,
               decoder_lm=None, lm_weight=0.0, word_bonus=0.0, token_beam=0, nst_min_confidence=None,
-              decoder_batched=False)
+              decoder_batched=False, device_wer=False)
 
 
 class HParams:
@@ -145,6 +154,14 @@ class HParams:
         Conformer's frame counts as lengths) instead of as one sequence over the batch.  A model option like
         use_group_norm: the parameters are the same, the decoder states are not."""
         self.decoder_batched = bool(flag)
+
+    def set_device_wer(self, flag):
+        """True: the Runner's metric is the corpus word error rate 100 * sum(errors) / sum(reference words) of an
+        epoch or split, from ctc.edit_distance on the device hypothesis ids (the greedy ids with <pad> / <blank>
+        stripped, or the best beam hypothesis) against the target ids, accumulated on the device together with the
+        loss: no host synchronisation per step.  Not the reference's figure (the mean over batches of a WER whose
+        targets are padded with '_'), which False (the default) keeps."""
+        self.device_wer = bool(flag)
 
     def set_ntokens(self, ntokens):
         self.ntokens = ntokens

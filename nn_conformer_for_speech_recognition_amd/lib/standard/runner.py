@@ -21,7 +21,13 @@ Same constructor, methods and control flow as the reference; what runs underneat
   confidence   hp.nst_min_confidence (default None: off): generate_labels force-aligns each beam hypothesis against
                the same logits and returns None for the labels whose mean per-frame log-probability along the best
                alignment is below the threshold; MelDataset.mix_datasets leaves those clips out.
-  WER          myvocab.wer (jiwer's sentence-list WER; jiwer is not in this image)
+  WER          myvocab.wer (jiwer's sentence-list WER; jiwer is not in this image).  hp.device_wer (default False:
+               that path, unchanged): ctc.edit_distance on the device hypothesis ids against the target ids; errors,
+               reference words and the loss accumulate in device tensors read once per epoch / split, and the figure
+               is the corpus WER 100 * sum(errors) / sum(words) (HParams.set_device_wer).
+  confusion    Runner.test(heatmap=True): the aligned pairs of ctc.edit_distance(ops=True) as a (V + 1, V + 1) count
+               matrix (row: reference word, column: hypothesis word, index V: the gap) on self.confusion[split] and
+               in hp.plots_dir/confusion_<split>.json (evals.py:64 builds it with sklearn and plots it).
 
 Dropped (outside the hot path): tqdm colours, Evals plots (losses / WER are kept on
 the Runner as .history and written to hp.plots_dir/history.json), the transformer-LM weight fusion (fuse_models).
@@ -37,7 +43,7 @@ from statistics import mean
 import torch
 import torch.nn as nn
 
-from ...ctc import CTCLoss, beam_search_decode, forced_align, greedy_decode
+from ...ctc import CTCLoss, beam_search_decode, edit_distance, forced_align, greedy_decode
 from ...optim import Adafactor
 from .myvocab import wer
 
@@ -69,6 +75,7 @@ class Runner:
         self.optimizer = Adafactor(model.parameters(), lr=hp.lr, beta1=hp.beta1, scale_parameter=hp.scale_parameter,
                                    relative_step=hp.relative_step)
         self.history = {"loss": [], "metric": [], "val_loss": [], "val_metric": []}
+        self.confusion = {}
 
     def set_model(self, model):
         self.__init__(model, self.hp)
@@ -95,10 +102,9 @@ class Runner:
                                   "path; for n-gram shallow fusion in the decoder see HParams.set_decoder_lm")
 
     # ----------------------------------------------------------------------------- train / test
-    def _beam_labels(self, voc, logits, lengths, confidence=False):
-        """hp.beam_size > 0: the best prefix-beam-search hypothesis per utterance as label strings (lengths: the
-        model's output lengths, padded / truncated to the batch; the kernel clamps them to [0, T]).  confidence (the
-        pseudo-label pass) with hp.nst_min_confidence set: None in place of a label whose confidence is below it."""
+    def _beam_search(self, voc, logits, lengths):
+        """The hp.beam_size search of the metric and label passes -> (fp32 logits, lengths padded / truncated to the
+        batch, tokens (B, 1, T) int32, counts (B, 1))."""
         if lengths is not None:
             B = logits.shape[0]
             lengths = nn.functional.pad(lengths[:B], (0, max(0, B - lengths.shape[0])))
@@ -110,6 +116,13 @@ class Runner:
         logits = logits.float() if logits.dtype != torch.float32 else logits
         toks, cnt, _ = beam_search_decode(logits, lengths, beam_size=int(self.hp.beam_size), blank=voc.blank_idx,
                                           pad=voc.pad_idx, **kw)
+        return logits, lengths, toks, cnt
+
+    def _beam_labels(self, voc, logits, lengths, confidence=False):
+        """hp.beam_size > 0: the best prefix-beam-search hypothesis per utterance as label strings (lengths: the
+        model's output lengths, padded / truncated to the batch; the kernel clamps them to [0, T]).  confidence (the
+        pseudo-label pass) with hp.nst_min_confidence set: None in place of a label whose confidence is below it."""
+        logits, lengths, toks, cnt = self._beam_search(voc, logits, lengths)
         labels = voc.decode(toks[:, 0], cnt[:, 0])
         thr = getattr(self.hp, "nst_min_confidence", None)
         if thr is None or not confidence:
@@ -138,15 +151,75 @@ class Runner:
         tw, pw = _word_lists(t_strs, p_strs)
         return wer(tw, pw) * 100 if tw else 0.0
 
+    # ----------------------------------------------------------------------------- device metric (hp.device_wer)
+    def _edit_distance(self, dataset, logits, target, target_lens, lengths=None, ops=False):
+        """ctc.edit_distance of the ids _metric decodes -- the greedy ids of every frame with <pad> / <blank> stripped
+        and no repeat collapse (hp.beam_size 0), else the best beam hypothesis -- against the target ids, over the
+        first min(rows of logits, rows of target) rows (the filter of _word_lists).  Nothing is read back.  The
+        hypothesis rows are as wide as the logits have frames: more than 1024 frames raise (ctc.EDIT_MAX_LEN)."""
+        voc = dataset.vocab
+        if getattr(self.hp, "beam_size", 0) > 0:
+            _, _, toks, cnt = self._beam_search(voc, logits, lengths)
+            toks, cnt = toks[:, 0], cnt[:, 0]
+        else:
+            x = logits.float() if logits.dtype != torch.float32 else logits
+            _, toks, cnt = greedy_decode(x, None, blank=voc.blank_idx, pad=voc.pad_idx, collapse=False)
+        n = min(toks.shape[0], target.shape[0])
+        return edit_distance(toks[:n], target[:n], cnt[:n], target_lens[:n], ops=ops)
+
+    def _new_accumulator(self):
+        """(words (2,) int64: word errors, reference words; loss () fp64: the sum of the steps' losses), on the
+        device."""
+        dev = self.hp.device
+        return torch.zeros(2, dtype=torch.int64, device=dev), torch.zeros((), dtype=torch.float64, device=dev)
+
+    @staticmethod
+    def _accumulate(acc, ed, loss):
+        """One step into the accumulators, nothing read back.  A row with an empty target contributes nothing
+        (_word_lists drops it); a NaN loss counts as 100 (runner.py:166).  ed None: the loss alone."""
+        words, loss_sum = acc
+        loss = loss.detach().reshape(())
+        loss_sum += torch.where(torch.isnan(loss), torch.full_like(loss, 100.0), loss).double()
+        if ed is not None:
+            counted = ed.ref_lengths > 0
+            words += torch.stack([(ed.distance * counted).sum(), ed.ref_lengths.sum()])
+
+    @staticmethod
+    def _read_accumulator(acc, steps):
+        """The one read of an epoch / split -> (mean loss, corpus WER %: 0.0 when there are no words)."""
+        (errors, words), loss = acc[0].tolist(), acc[1].item()
+        return (loss / steps if steps else float("nan")), (100.0 * errors / words if words > 0 else 0.0)
+
+    def _confusion_add(self, conf, ed, V):
+        """conf (V + 1, V + 1) int64 += the aligned pairs of ed (ops=True): row = reference word, column =
+        hypothesis word, index V = the gap.  Rows with an empty target are left out, as in the metric."""
+        ldp = ed.pair_ref.shape[-1]
+        live = (torch.arange(ldp, device=conf.device)[None, :] < ed.n_pairs[:, None]) & (ed.ref_lengths > 0)[:, None]
+        r = torch.where(ed.pair_ref < 0, V, ed.pair_ref).clamp(max=V).long()
+        h = torch.where(ed.pair_hyp < 0, V, ed.pair_hyp).clamp(max=V).long()
+        conf.view(-1).index_add_(0, (r * (V + 1) + h).reshape(-1), live.reshape(-1).long())
+
+    def _write_confusion(self, dataset, dataset_type, conf):
+        V = conf.shape[0] - 1
+        itos = list(dataset.vocab.itos)
+        labels = [itos[i] if i < len(itos) else str(i) for i in range(V)] + ["<gap>"]
+        self.confusion[dataset_type] = conf.cpu()
+        d = getattr(self.hp, "plots_dir", None)
+        if d:
+            with open(os.path.join(d, f"confusion_{dataset_type}.json"), "w") as f:
+                json.dump({"labels": labels, "matrix": self.confusion[dataset_type].tolist()}, f)
+
     def train(self, train_set, epochs, SpecAugment=False, use_mix=False, finetuning=False):
         """runner.py:102-182."""
         dataset_type = "mix" if use_mix else "train"
         train_size = ceil(len(train_set.idxes[dataset_type]) / self.hp.batch_size)
         want_wer = getattr(self.hp, "train_wer", True)     # WER forces a host sync per step (SURVEY §5)
+        device_wer = bool(getattr(self.hp, "device_wer", False))
         for _ in range(epochs):
             self.model.train()
             train_set.shuffle(dataset_type)
             eloss, emetric = [], []
+            acc = self._new_accumulator() if device_wer else None
             for i in range(train_size):
                 batch = train_set.get_batch(i, dataset_type)
                 inbatch, input_lens = batch["input"]["mels"], batch["input"]["tau"]
@@ -156,6 +229,14 @@ class Runner:
                 output_lengths = nn.functional.pad(output_lengths, (0, self.hp.batch_size - output_lengths.shape[0]))
                 output_lengths = output_lengths.clamp(max=logits.shape[1])
                 loss = self.loss(logits.transpose(0, 1), target, output_lengths, target_lens)
+                if device_wer:     # loss and word errors stay on the device: no host sync in the step
+                    loss.backward()
+                    self.optimizer.step()
+                    with torch.no_grad():
+                        ed = self._edit_distance(train_set, logits.detach(), target, target_lens,
+                                                 output_lengths) if want_wer else None
+                        self._accumulate(acc, ed, loss)
+                    continue
                 cur = loss.item()
                 loss.backward()
                 self.optimizer.step()
@@ -163,8 +244,13 @@ class Runner:
                 if want_wer:
                     emetric.append(self._metric(train_set, logits.detach(), target, output_lengths))
             self._check_device_errors()
-            self.history["loss"].append(mean([100 if isnan(x) else x for x in eloss]))
-            self.history["metric"].append(mean(emetric) if emetric else float("nan"))
+            if device_wer:
+                eloss, emetric = self._read_accumulator(acc, train_size)
+                self.history["loss"].append(eloss)
+                self.history["metric"].append(emetric if want_wer else float("nan"))
+            else:
+                self.history["loss"].append(mean([100 if isnan(x) else x for x in eloss]))
+                self.history["metric"].append(mean(emetric) if emetric else float("nan"))
             if "validation" in train_set.idxes:
                 vl, vm = self.test(train_set, "validation", finetuning=finetuning)
                 self.history["val_loss"].append(vl)
@@ -174,10 +260,14 @@ class Runner:
             self.save_model(finetuning)
 
     def test(self, test_set, dataset_type="test", heatmap=False, finetuning=False):
-        """runner.py:183-252 -> (mean loss, mean WER %)."""
+        """runner.py:183-252 -> (mean loss, mean WER %); with hp.device_wer (mean loss, corpus WER %).  heatmap: the
+        split's confusion matrix on self.confusion[dataset_type] and in hp.plots_dir (see the module docstring)."""
         self.model.eval()
         n = ceil(len(test_set.idxes[dataset_type]) / self.hp.batch_size)
         eloss, emetric = [], []
+        device_wer = bool(getattr(self.hp, "device_wer", False))
+        acc = self._new_accumulator() if device_wer else None
+        conf = None
         with torch.no_grad():
             for i in range(n):
                 batch = test_set.get_batch(i, dataset_type)
@@ -187,9 +277,23 @@ class Runner:
                 output_lens = nn.functional.pad(output_lens, (0, self.hp.batch_size - output_lens.shape[0]))
                 output_lens = output_lens.clamp(max=logits.shape[1])
                 loss = self.loss(logits.transpose(0, 1), target, output_lens, target_lens)
+                if heatmap or device_wer:
+                    ed = self._edit_distance(test_set, logits, target, target_lens, output_lens, ops=heatmap)
+                if heatmap:
+                    V = logits.shape[-1]
+                    if conf is None:
+                        conf = torch.zeros(V + 1, V + 1, dtype=torch.int64, device=logits.device)
+                    self._confusion_add(conf, ed, V)
+                if device_wer:
+                    self._accumulate(acc, ed, loss)
+                    continue
                 eloss.append(loss.item())
                 emetric.append(self._metric(test_set, logits, target, output_lens))
         self._check_device_errors()
+        if conf is not None:
+            self._write_confusion(test_set, dataset_type, conf)
+        if device_wer:
+            return self._read_accumulator(acc, n)
         eloss = mean([100 if isnan(x) else x for x in eloss])
         return eloss, mean(emetric)
 

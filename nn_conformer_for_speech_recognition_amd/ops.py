@@ -1149,3 +1149,35 @@ def ctc_forced_align(x, targets_i32, ldt, tgt_off, in_len_i32, tgt_len_i32, smax
            L.ptr(tgt_len_i32), B, T, x.shape[-1], int(smax), int(blank), L.ptr(alignments), L.ptr(scores), L.ptr(score),
            L.ptr(starts), L.ptr(ends), L.ptr(token_scores), L.ptr(ws), L.stream())
     return alignments, scores, score, starts, ends, token_scores
+
+
+def edit_distance(ref_i32, ldr, ref_len_i32, hyp_i32, ldh, hyp_len_i32, P, group, rmax, hmax, want_ops=False,
+                  out=None):
+    """Batched edit distance over token ids (cfm_edit_distance): pair p compares hypothesis row p (hyp_i32 + p * ldh)
+    with reference row p // group.  -> (dist (P,), counts (P, 4), pair_ref (P, rmax + hmax), pair_hyp, n_pairs (P,)),
+    all int32; the last four None unless want_ops.  out: optional dict of caller-allocated int32 outputs under those
+    names (e.g. views into a larger buffer)."""
+    dev = hyp_len_i32.device
+    out = out or {}
+    ldp = int(rmax) + int(hmax)
+
+    def buf(name, *shape):
+        t = out.get(name)
+        if t is None:
+            return torch.empty(*shape, device=dev, dtype=torch.int32)
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise L.CfmError(f"edit_distance: out[{name!r}] must be a contiguous int32 tensor of shape {shape}")
+        return t
+
+    dist = buf("dist", P)
+    counts = pair_ref = pair_hyp = n_pairs = None
+    if want_ops:
+        counts, n_pairs = buf("counts", P, 4), buf("n_pairs", P)
+        pair_ref, pair_hyp = buf("pair_ref", P, ldp), buf("pair_hyp", P, ldp)
+    nbytes = L.size_call("cfm_edit_distance_ws_bytes", P, int(rmax), int(hmax), int(bool(want_ops)))
+    ws = workspace(nbytes, dev) if nbytes else None
+    if P > 0:   # (an empty batch has no buffers to point at)
+        L.call("cfm_edit_distance", L.ptr(ref_i32) or None, int(ldr), L.ptr(ref_len_i32), P // group,
+               L.ptr(hyp_i32) or None, int(ldh), L.ptr(hyp_len_i32), P, int(group), int(rmax), int(hmax), L.ptr(dist),
+               L.ptr(counts), L.ptr(pair_ref), L.ptr(pair_hyp), ldp, L.ptr(n_pairs), L.ptr(ws), L.stream())
+    return dist, counts, pair_ref, pair_hyp, n_pairs
