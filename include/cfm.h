@@ -825,7 +825,9 @@ int cfm_adafactor_step_ex(const void* dev_table, int n, long nrow_tasks, long nc
  *      ws: cfm_ctc_ws_bytes(B, T, Smax) bytes, read again by the backward.
  * bwd: grad[b, t, v] = (softmax - posterior) * grad_out[b * grad_out_stride] * r_b with
  *      r_b = 1 / (B * max(L_b, 1)) for reduction 1 (mean), 1 for 0 (none) / 2 (sum); zero for
- *      t >= in_len[b] and for zeroed infinite losses.  Output layout gsb/gst, dtype_grad f32|bf16. */
+ *      t >= in_len[b] and for zeroed infinite losses.  Output layout gsb/gst, dtype_grad f32|bf16.
+ *      The backward checks B, T, V, Smax, ldt and blank as the forward does (same codes, its own name in the
+ *      message): it rejects only calls whose forward, which fills the workspace it reads, was rejected too. */
 size_t cfm_ctc_ws_bytes(int B, int T, int Smax);
 int cfm_ctc_loss_fwd(const float* logits, long sb, long st, const int32_t* targets, int ldt,
                      const int32_t* tgt_off, const int32_t* in_len, const int32_t* tgt_len, int B,

@@ -43,10 +43,12 @@ int num_cus();
 
 #define CFM_EXPORT extern "C" __attribute__((visibility("default")))
 
-#define CFM_REQUIRE(cond, code, msg)                                  \
+// CFM_REQUIRE_FN: for a helper that checks on behalf of the entry point named fn
+#define CFM_REQUIRE_FN(fn, cond, code, msg)                           \
   do {                                                                \
-    if (!(cond)) return cfm::fail((code), std::string(__func__) + ": " + (msg)); \
+    if (!(cond)) return cfm::fail((code), std::string(fn) + ": " + (msg)); \
   } while (0)
+#define CFM_REQUIRE(cond, code, msg) CFM_REQUIRE_FN(__func__, cond, code, msg)
 
 // ----------------------------------------------------------------------------- conversions
 __device__ __forceinline__ float to_f32(float x) { return x; }
@@ -218,5 +220,14 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+
+// ----------------------------------------------------------------------------- one-lane wave shifts
+// wave_shr1: lane l <- lane l - 1; wave_shl1: lane l <- lane l + 1 (DPP wave_shr:1 / wave_shl:1, one instruction,
+// no LDS).  All lanes must take part.  The lane with no source (lane 0 / lane 63) receives 0 and is overwritten by
+// the caller.
+__device__ __forceinline__ int wave_shr1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xF, 0xF, true); }
+__device__ __forceinline__ int wave_shl1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x130, 0xF, 0xF, true); }
+__device__ __forceinline__ float wave_shr1(float v) { return __int_as_float(wave_shr1(__float_as_int(v))); }
+__device__ __forceinline__ float wave_shl1(float v) { return __int_as_float(wave_shl1(__float_as_int(v))); }
 
 __host__ __device__ static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }

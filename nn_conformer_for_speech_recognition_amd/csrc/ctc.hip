@@ -18,20 +18,12 @@
 //   ctc_grad     one workgroup per frame row: grad[v] = (exp(logit - lse) - sum_{s: l'(s)=v}
 //                exp(alpha + beta + nll - lpe)) * scale; duplicate labels are summed in label order
 //                (deterministic, no atomics)
-#include "cfm_common.h"
+#include "ctc_common.h"
 
-#include <math.h>
+using namespace ctc;
 
 namespace {
 
-constexpr float NEG_INF = -INFINITY;
-constexpr int PF = 16;   // frames of lpe prefetched per chunk
-
-__device__ __forceinline__ float lse2(float a, float b) {
-  const float m = fmaxf(a, b);
-  if (m == NEG_INF) return NEG_INF;
-  return m + logf(expf(a - m) + expf(b - m));
-}
 // the alpha / beta recursion's 3-way log-sum-exp on the hardware exp2 / log2 (v_exp_f32 / v_log_f32: the
 // arguments are <= 0 and the sum is in [1, 3], where both are accurate to about an ulp): the libm expf / logf
 // range reductions made this the recursion's critical path (one barrier-separated frame per ~0.9 us at L60)
@@ -53,16 +45,7 @@ __device__ __forceinline__ float lse3(float a, float b, float c) {
   return m + __builtin_amdgcn_logf(s) * LN2F;
 }
 
-// extended label of state s
-// (defined after CtcP: ext_label clamps the label ids)
-
-struct CtcP {
-  const float* logits; long sb, st;   // row (b, t) at logits + b*sb + t*st (batch- or time-major)
-  const int32_t* tgt; int ldt;        // targets: utterance b at tgt + (off ? off[b] : b*ldt)
-  const int32_t* off;
-  const int32_t* in_len; const int32_t* tgt_len;
-  int B, T, V, Smax, S;               // S = 2*Smax + 1 (state stride of the work arrays)
-  int blank;
+struct CtcP : CtcView {
   float* lse;                         // (B, T)
   float* lpe;                         // (B, T, S)
   float* alpha;                       // (B, T, S)
@@ -74,53 +57,11 @@ struct CtcP {
   int dbg_abort;                      // debug (cfm_ctc_set_debug): bit d forces direction d's abort path
 };
 
-__device__ __forceinline__ const int32_t* tgt_of(const CtcP& p, int b) {
-  return p.tgt + (p.off ? (long)p.off[b] : (long)b * p.ldt);
-}
-// lengths are device data: clamp to the buffers' extents (in_len <= T, tgt_len <= Smax) so that a bad
-// length can only give a wrong loss, never an access outside lpe / alpha / beta / sh[] (torch raises
-// on such inputs; the host wrapper validates host-side lengths the same way)
-__device__ __forceinline__ int in_len_of(const CtcP& p, int b) { return min(max(p.in_len[b], 0), p.T); }
-__device__ __forceinline__ int tgt_len_of(const CtcP& p, int b) { return min(max(p.tgt_len[b], 0), p.Smax); }
-// label u of an utterance, clamped to the class range (an out-of-range id would index x / corr[] out of bounds)
-__device__ __forceinline__ int label_of(const CtcP& p, const int32_t* tg, int u) { return min(max(tg[u], 0), p.V - 1); }
-__device__ __forceinline__ int ext_label(const CtcP& p, const int32_t* tg, int s) { return (s & 1) ? label_of(p, tg, s >> 1) : p.blank; }
-
 // ---------------------------------------------------------------------------------- prep
+// lpe = x - lse through the row's lse = m + log(sum), which is stored: ctc_grad's softmax is exp(x - lse) of the same
+// lse (the loss tests compare this form against torch; the aligner's form differs, see align_prep)
 __global__ __launch_bounds__(256) void ctc_prep(CtcP p) {
-  const int lane = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= (long)p.B * p.T) return;
-  const int b = (int)(row / p.T), t = (int)(row % p.T);
-  if (t >= in_len_of(p, b)) return;
-  const float* x = p.logits + b * p.sb + t * p.st;
-  float m = NEG_INF;
-  const bool v4 = (p.V % 4 == 0) && (p.sb % 4 == 0) && (p.st % 4 == 0) && ((uintptr_t)p.logits % 16 == 0);
-  if (v4) {
-    for (int v = lane * 4; v < p.V; v += 256) {
-      const float4 q = *reinterpret_cast<const float4*>(x + v);
-      m = fmaxf(m, fmaxf(fmaxf(q.x, q.y), fmaxf(q.z, q.w)));
-    }
-  } else {
-    for (int v = lane; v < p.V; v += 64) m = fmaxf(m, x[v]);
-  }
-  m = wave_max(m);
-  float s = 0.f;
-  if (v4) {
-    for (int v = lane * 4; v < p.V; v += 256) {
-      const float4 q = *reinterpret_cast<const float4*>(x + v);
-      s += expf(q.x - m) + expf(q.y - m) + expf(q.z - m) + expf(q.w - m);
-    }
-  } else {
-    for (int v = lane; v < p.V; v += 64) s += expf(x[v] - m);
-  }
-  s = wave_sum(s);
-  const float l = m + logf(s);
-  if (lane == 0) p.lse[row] = l;
-  const int Sb = 2 * tgt_len_of(p, b) + 1;
-  const int32_t* tg = tgt_of(p, b);
-  float* dst = p.lpe + row * p.S;
-  for (int st = lane; st < Sb; st += 64) dst[st] = x[ext_label(p, tg, st)] - l;
+  prep_row(p, p.lpe, p.lse, [](float x, float m, float ls) { return x - (m + ls); });
 }
 
 // ---------------------------------------------------------------------------------- alpha / beta
@@ -136,7 +77,7 @@ __global__ __launch_bounds__(256) void ctc_prep(CtcP p) {
 // (nll and the nll_raw ctc_grad reads) into NaN and counts it in the bound abort counter (cfm_ctc_bind_abort_counter),
 // apart from genuine non-finite losses.  AB_SPIN polls of s_sleep 1 are ~0.1 s: a delayed co-resident wave
 // (a side-stream kernel sharing the CU) slows the step, it does not abort it.
-constexpr int AB_NT = 1024;
+constexpr int AB_NT = CTC_MAX_STATES;
 constexpr int AB_RB = 4;                  // ring depth in blocks
 constexpr int AB_RF = AB_RB * PF;         // ring depth in frames
 constexpr int AB_SPIN = 1 << 22;
@@ -178,16 +119,12 @@ __device__ __forceinline__ void ctc_alphabeta_dir(const CtcP& p, float* edge_mem
   };
   // lpe of this state, PF frames per block prefetched one block ahead (unconditional clamped loads)
   float cur[PF], nxt[PF];
-  auto fetch = [&](float (&r)[PF], int i0) {
-#pragma unroll
-    for (int q = 0; q < PF; ++q) r[q] = lp[(long)frame(min(i0 + q, Tb - 1)) * p.S + sc];
-  };
   const int nsteps = w < nw ? Tb : 0;
   float prev = NEG_INF;
-  if (nsteps) fetch(cur, 0);
+  if (nsteps) fetch_lpe(cur, lp, p.S, sc, 0, Tb, frame);
   for (int i0 = 0; i0 < nsteps; i0 += PF) {
     const int kb = i0 / PF;
-    fetch(nxt, min(i0 + PF, Tb - 1));
+    fetch_lpe(nxt, lp, p.S, sc, min(i0 + PF, Tb - 1), Tb, frame);
     // the predecessor's edge pairs of frames i0 - 1 .. i0 + PF - 2, frame i0 - 1 + j in lane j
     float ex = NEG_INF, ey = NEG_INF, ev[PF];
     if (has_pred) {
@@ -209,10 +146,9 @@ __device__ __forceinline__ void ctc_alphabeta_dir(const CtcP& p, float* edge_mem
       // the edge lanes get -inf, then the predecessor's pair
       // (the shifts write 0 into the edge lanes, which the predecessor's pair then replaces -- -inf for the first
       // wave, whose ex / ey stay -inf: no old-value moves and no branch on has_pred)
-      constexpr int SH = DIR == 0 ? 0x138 : 0x130;
       constexpr int l0 = DIR == 0 ? 0 : 63, l1 = DIR == 0 ? 1 : 62;
-      float n1 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(prev), SH, 0xF, 0xF, true));
-      float n2 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(n1), SH, 0xF, 0xF, true));
+      float n1 = DIR == 0 ? wave_shr1(prev) : wave_shl1(prev);
+      float n2 = DIR == 0 ? wave_shr1(n1) : wave_shl1(n1);
       const float e0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ex), q));
       const float e1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ey), q));
       n1 = lane == l0 ? e0 : n1;
@@ -435,6 +371,9 @@ __global__ void greedy_compact(const int64_t* __restrict__ ids, const int32_t* _
                                int blank, int pad, int collapse, int32_t* __restrict__ out, int32_t* __restrict__ out_len) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
+  // no lower bound here, unlike clamp_len: a negative length runs the loop below zero times and Tb is used nowhere
+  // else.  With clamp_len's v_max the decode measured 1.1 to 1.4 % slower at 8 x 1498 frames, outside the parent's
+  // own spread (profiles/ctc_common/speed.txt), so the kernel keeps its instruction stream.
   const int Tb = lens ? min(lens[b], T) : T;
   int n = 0;
   long prev = -1;
@@ -449,20 +388,34 @@ __global__ void greedy_compact(const int64_t* __restrict__ ids, const int32_t* _
   out_len[b] = n;
 }
 
-CtcP make_p(const float* logits, long sb, long st, const int32_t* targets, int ldt, const int32_t* off,
-            const int32_t* in_len, const int32_t* tgt_len, int B, int T, int V, int Smax, int blank, float* ws) {
+// the workspace, as byte offsets: cfm_ctc_ws_bytes and make_p both read this
+struct CtcWs { size_t lse, lpe, alpha, beta, nll_raw, grp, ab_abort, total; };
+CtcWs ctc_ws(int B, int T, int Smax) {
+  const size_t bt = (size_t)B * T, bts = bt * (2 * (size_t)Smax + 1);
+  CtcWs w;
+  w.lse = 0;
+  w.lpe = w.lse + sizeof(float) * bt;
+  w.alpha = w.lpe + sizeof(float) * bts;
+  w.beta = w.alpha + sizeof(float) * bts;
+  w.nll_raw = w.beta + sizeof(float) * bts;
+  w.grp = w.nll_raw + sizeof(float) * (size_t)B;
+  w.ab_abort = w.grp + sizeof(int32_t) * 2 * (size_t)B * Smax;
+  w.total = w.ab_abort + sizeof(int32_t) * 2 * (size_t)B;
+  return w;
+}
+
+CtcP make_p(const CtcView& v, float* ws) {
   CtcP p;
-  p.logits = logits; p.sb = sb; p.st = st; p.tgt = targets; p.ldt = ldt; p.off = off;
-  p.in_len = in_len; p.tgt_len = tgt_len;
-  p.B = B; p.T = T; p.V = V; p.Smax = Smax; p.S = 2 * Smax + 1; p.blank = blank;
-  const long bt = (long)B * T, bts = bt * p.S;
-  p.lse = ws;
-  p.lpe = ws + bt;
-  p.alpha = p.lpe + bts;
-  p.beta = p.alpha + bts;
-  p.nll_raw = p.beta + bts;
-  p.grp = reinterpret_cast<int32_t*>(p.nll_raw + B);
-  p.ab_abort = p.grp + 2L * B * Smax;
+  static_cast<CtcView&>(p) = v;
+  const CtcWs w = ctc_ws(v.B, v.T, v.Smax);
+  char* base = reinterpret_cast<char*>(ws);
+  p.lse = reinterpret_cast<float*>(base + w.lse);
+  p.lpe = reinterpret_cast<float*>(base + w.lpe);
+  p.alpha = reinterpret_cast<float*>(base + w.alpha);
+  p.beta = reinterpret_cast<float*>(base + w.beta);
+  p.nll_raw = reinterpret_cast<float*>(base + w.nll_raw);
+  p.grp = reinterpret_cast<int32_t*>(base + w.grp);
+  p.ab_abort = reinterpret_cast<int32_t*>(base + w.ab_abort);
   p.dbg_abort = 0;
   return p;
 }
@@ -472,11 +425,7 @@ int32_t* g_ctc_aborts = nullptr;  // cfm_ctc_bind_abort_counter
 
 }  // namespace
 
-CFM_EXPORT size_t cfm_ctc_ws_bytes(int B, int T, int Smax) {
-  const long bt = (long)B * T;
-  return sizeof(float) * (size_t)(bt + 3 * bt * (2L * Smax + 1) + B) + sizeof(int32_t) * 2 * (size_t)B * Smax +
-         sizeof(int32_t) * 2 * (size_t)B;
-}
+CFM_EXPORT size_t cfm_ctc_ws_bytes(int B, int T, int Smax) { return ctc_ws(B, T, Smax).total; }
 
 CFM_EXPORT int cfm_ctc_set_debug(int force_abort_mask) {
   CFM_REQUIRE(force_abort_mask >= 0 && force_abort_mask <= 3, CFM_ERR_ARG, "mask: bit 0 alpha, bit 1 beta");
@@ -493,12 +442,10 @@ CFM_EXPORT int cfm_ctc_loss_fwd(const float* logits, long sb, long st, const int
                                 const int32_t* tgt_off, const int32_t* in_len, const int32_t* tgt_len, int B, int T,
                                 int V, int Smax, int blank, int zero_infinity, float* nll, float* ws, void* stream) {
   CFM_REQUIRE(logits && targets && in_len && tgt_len && nll && ws, CFM_ERR_ARG, "null pointer");
-  CFM_REQUIRE(B > 0 && T > 0 && V > 0 && Smax >= 0 && (tgt_off || ldt >= Smax), CFM_ERR_SHAPE, "bad shape");
-  CFM_REQUIRE(blank >= 0 && blank < V, CFM_ERR_ARG, "blank out of range");
-  const int S = 2 * Smax + 1;
-  CFM_REQUIRE(S <= AB_NT, CFM_ERR_UNSUPPORTED, "target length must be <= 511");
+  const CtcView v = make_view(logits, sb, st, targets, ldt, tgt_off, in_len, tgt_len, B, T, V, Smax, blank);
+  if (const int rc = check_ctc_problem(__func__, v)) return rc;
   hipStream_t s = cfm::as_stream(stream);
-  CtcP p = make_p(logits, sb, st, targets, ldt, tgt_off, in_len, tgt_len, B, T, V, Smax, blank, ws);
+  CtcP p = make_p(v, ws);
   p.dbg_abort = g_ctc_dbg_abort;
   hipLaunchKernelGGL(ctc_prep, dim3((unsigned)(((long)B * T + 3) / 4)), dim3(256), 0, s, p);
   hipLaunchKernelGGL(ctc_alphabeta, dim3(B, 2), dim3(AB_NT), 0, s, p);
@@ -513,11 +460,12 @@ CFM_EXPORT int cfm_ctc_loss_bwd(const float* logits, long sb, long st, const int
                                 int grad_out_stride, int reduction, void* grad_logits, int dtype_grad, long gsb,
                                 long gst, void* stream) {
   CFM_REQUIRE(logits && targets && in_len && tgt_len && ws && grad_out && grad_logits, CFM_ERR_ARG, "null pointer");
-  CFM_REQUIRE(B > 0 && T > 0 && V > 0, CFM_ERR_SHAPE, "bad shape");
+  const CtcView v = make_view(logits, sb, st, targets, ldt, tgt_off, in_len, tgt_len, B, T, V, Smax, blank);
+  if (const int rc = check_ctc_problem(__func__, v)) return rc;
   CFM_REQUIRE(reduction >= 0 && reduction <= 2, CFM_ERR_ARG, "reduction: 0 none / 1 mean / 2 sum");
   CFM_REQUIRE((size_t)V * sizeof(float) <= 64 * 1024, CFM_ERR_UNSUPPORTED, "V too large for the LDS row");
   hipStream_t s = cfm::as_stream(stream);
-  CtcP p = make_p(logits, sb, st, targets, ldt, tgt_off, in_len, tgt_len, B, T, V, Smax, blank, const_cast<float*>(ws));
+  CtcP p = make_p(v, const_cast<float*>(ws));
   const size_t sh = (size_t)V * sizeof(float);
   const dim3 grid((unsigned)((long)B * T));
   if (Smax > 0) hipLaunchKernelGGL(ctc_group, dim3(B), dim3(256), (size_t)((Smax + 15) & ~15) * sizeof(int), s, p);

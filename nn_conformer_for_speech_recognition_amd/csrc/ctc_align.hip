@@ -5,8 +5,8 @@
 // Kernels (B utterances, T frames, V classes, L_b target labels, S_b = 2 L_b + 1 states: blank, l1, blank, ...):
 //   align_prep       one wave per frame row: m = max, sum = sum exp(x - m) of the logits row; lpe[b,t,s] = (logit of
 //                    the s-th extended label - m) - log(sum): the log-softmax ctc_prep of ctc.hip produces, in the
-//                    form whose roundings scale with the result (a prep of this file's own: ctc.hip stays as it
-//                    is)                                                                      HBM: one row read
+//                    form whose roundings scale with the result (the row sweep is ctc_common.h's prep_row; the
+//                    last expression is this kernel's)                                        HBM: one row read
 //   align_viterbi    one workgroup per utterance, one state per thread, the time loop sequential: the max-plus
 //                    recursion v[t,s] = lpe[t,s] + max(v[t-1,s], v[t-1,s-1], v[t-1,s-2] if allowed) with the chosen
 //                    move (0 stay, 1 from s-1, 2 from s-2) stored per (t, s) as one byte.  <true>: S <= 64, one wave,
@@ -22,76 +22,27 @@
 //                    the per-token sums follow in frame order, one thread per token (no atomics: deterministic).
 // Tie rule (part of the contract): equal predecessors prefer stay, then s-1, then s-2; at the end the final blank
 // S_b-1 wins a tie against S_b-2.
-#include "cfm_common.h"
+#include "ctc_common.h"
 
-#include <math.h>
+using namespace ctc;
 
 namespace {
 
-constexpr float NEG_INF = -INFINITY;
-constexpr int PF = 16;        // frames of lpe prefetched per chunk (as the loss)
-constexpr int VT_NT = 1024;   // largest block of the recursion: 2 * 511 + 1 states
+constexpr int VT_NT = CTC_MAX_STATES;   // largest block of the recursion
 constexpr int BT_F = 32;      // frames per chunk of the backtrace: the state drops by <= 2 (BT_F - 1) = 62 < 64
 
-struct AlignP {
-  const float* logits; long sb, st;   // row (b, t) at logits + b*sb + t*st (batch- or time-major)
-  const int32_t* tgt; int ldt;        // targets: utterance b at tgt + (off ? off[b] : b*ldt)
-  const int32_t* off;
-  const int32_t* in_len; const int32_t* tgt_len;
-  int B, T, V, Smax, S;               // S = 2*Smax + 1 (state stride of the work arrays)
-  int blank;
+struct AlignP : CtcView {
   float* lpe;                         // (B, T, S)
   int32_t* end_state;                 // (B) state of the last frame; -1: no alignment (infeasible)
   uint8_t* moves;                     // (B, T, S) 0 stay / 1 from s-1 / 2 from s-2
 };
 
-__device__ __forceinline__ const int32_t* tgt_of(const AlignP& p, int b) {
-  return p.tgt + (p.off ? (long)p.off[b] : (long)b * p.ldt);
-}
-// lengths and labels are device data, clamped exactly as in ctc.hip: a bad value can give a wrong answer, never an
-// access outside logits / lpe / moves / the outputs
-__device__ __forceinline__ int in_len_of(const AlignP& p, int b) { return min(max(p.in_len[b], 0), p.T); }
-__device__ __forceinline__ int tgt_len_of(const AlignP& p, int b) { return min(max(p.tgt_len[b], 0), p.Smax); }
-__device__ __forceinline__ int label_of(const AlignP& p, const int32_t* tg, int u) { return min(max(tg[u], 0), p.V - 1); }
-__device__ __forceinline__ int ext_label(const AlignP& p, const int32_t* tg, int s) { return (s & 1) ? label_of(p, tg, s >> 1) : p.blank; }
-
 // ---------------------------------------------------------------------------------- emissions
 __global__ __launch_bounds__(256) void align_prep(AlignP p) {
-  const int lane = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= (long)p.B * p.T) return;
-  const int b = (int)(row / p.T), t = (int)(row % p.T);
-  if (t >= in_len_of(p, b)) return;
-  const float* x = p.logits + b * p.sb + t * p.st;
-  float m = NEG_INF;
-  const bool v4 = (p.V % 4 == 0) && (p.sb % 4 == 0) && (p.st % 4 == 0) && ((uintptr_t)p.logits % 16 == 0);
-  if (v4) {
-    for (int v = lane * 4; v < p.V; v += 256) {
-      const float4 q = *reinterpret_cast<const float4*>(x + v);
-      m = fmaxf(m, fmaxf(fmaxf(q.x, q.y), fmaxf(q.z, q.w)));
-    }
-  } else {
-    for (int v = lane; v < p.V; v += 64) m = fmaxf(m, x[v]);
-  }
-  m = wave_max(m);
-  float s = 0.f;
-  if (v4) {
-    for (int v = lane * 4; v < p.V; v += 256) {
-      const float4 q = *reinterpret_cast<const float4*>(x + v);
-      s += expf(q.x - m) + expf(q.y - m) + expf(q.z - m) + expf(q.w - m);
-    }
-  } else {
-    for (int v = lane; v < p.V; v += 64) s += expf(x[v] - m);
-  }
-  s = wave_sum(s);
   // (x - m) - log(sum), not x - (m + log(sum)): both terms are <= 0 and no larger than the result, so every rounding is
   // relative to the log-probability itself; through lse = m + log(sum) it would be relative to |lse|, which for raw
   // logits with an offset is far above a confident frame's log-probability (and above a short path's whole score)
-  const float ls = logf(s);
-  const int Sb = 2 * tgt_len_of(p, b) + 1;
-  const int32_t* tg = tgt_of(p, b);
-  float* dst = p.lpe + row * p.S;
-  for (int st = lane; st < Sb; st += 64) dst[st] = (x[ext_label(p, tg, st)] - m) - ls;
+  prep_row(p, p.lpe, nullptr, [](float x, float m, float ls) { return (x - m) - ls; });
 }
 
 // ---------------------------------------------------------------------------------- Viterbi recursion
@@ -126,14 +77,11 @@ __global__ __launch_bounds__(ONE ? 64 : VT_NT) void align_viterbi(AlignP p, floa
   }
   // lpe of this state, PF frames per block prefetched one block ahead (unconditional clamped loads)
   float cur[PF], nxt[PF];
-  auto fetch = [&](float (&r)[PF], int i0) {
-#pragma unroll
-    for (int q = 0; q < PF; ++q) r[q] = lp[(long)min(i0 + q, Tb - 1) * p.S + sc];
-  };
+  auto frame = [](int i) { return i; };
   float prev = NEG_INF;
-  fetch(cur, 0);
+  fetch_lpe(cur, lp, p.S, sc, 0, Tb, frame);
   for (int i0 = 0; i0 < Tb; i0 += PF) {
-    fetch(nxt, min(i0 + PF, Tb - 1));
+    fetch_lpe(nxt, lp, p.S, sc, min(i0 + PF, Tb - 1), Tb, frame);
 #pragma unroll
     for (int q = 0; q < PF; ++q) {
       const int i = i0 + q;
@@ -141,8 +89,8 @@ __global__ __launch_bounds__(ONE ? 64 : VT_NT) void align_viterbi(AlignP p, floa
       float n1, n2;
       if (ONE) {
         // lane l <- lane l - 1 (wave_shr; the shifted-in lanes are set to -inf)
-        n1 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(prev), 0x138, 0xF, 0xF, true));
-        n2 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(n1), 0x138, 0xF, 0xF, true));
+        n1 = wave_shr1(prev);
+        n2 = wave_shr1(n1);
         n1 = lane < 1 ? NEG_INF : n1;
         n2 = lane < 2 ? NEG_INF : n2;
       } else {
@@ -280,20 +228,16 @@ CFM_EXPORT int cfm_ctc_forced_align(const float* logits, long sb, long st, const
                                     int V, int Smax, int blank, int32_t* alignments, float* scores, float* score,
                                     int32_t* starts, int32_t* ends, float* token_scores, void* ws, void* stream) {
   CFM_REQUIRE(logits && in_len && tgt_len && alignments && scores && score && ws, CFM_ERR_ARG, "null pointer");
-  CFM_REQUIRE(B > 0 && T > 0 && V > 0 && Smax >= 0 && (tgt_off || ldt >= Smax), CFM_ERR_SHAPE, "bad shape");
   CFM_REQUIRE(targets || Smax == 0, CFM_ERR_ARG, "null targets");
-  CFM_REQUIRE(blank >= 0 && blank < V, CFM_ERR_ARG, "blank out of range");
   CFM_REQUIRE((starts != nullptr) == (ends != nullptr) && (ends != nullptr) == (token_scores != nullptr), CFM_ERR_ARG,
               "starts, ends and token_scores: all three or none");
-  const int S = 2 * Smax + 1;
-  CFM_REQUIRE(S <= VT_NT, CFM_ERR_UNSUPPORTED, "target length must be <= 511");
+  AlignP p;
+  static_cast<CtcView&>(p) = make_view(logits, sb, st, targets, ldt, tgt_off, in_len, tgt_len, B, T, V, Smax, blank);
+  if (const int rc = check_ctc_problem(__func__, p)) return rc;
+  const int S = p.S;
   hipStream_t s = cfm::as_stream(stream);
   const AlignWs w = align_ws(B, T, Smax);
   char* base = static_cast<char*>(ws);
-  AlignP p;
-  p.logits = logits; p.sb = sb; p.st = st; p.tgt = targets; p.ldt = ldt; p.off = tgt_off;
-  p.in_len = in_len; p.tgt_len = tgt_len;
-  p.B = B; p.T = T; p.V = V; p.Smax = Smax; p.S = S; p.blank = blank;
   p.lpe = reinterpret_cast<float*>(base + w.lpe);
   p.end_state = reinterpret_cast<int32_t*>(base + w.end_state);
   p.moves = reinterpret_cast<uint8_t*>(base + w.moves);

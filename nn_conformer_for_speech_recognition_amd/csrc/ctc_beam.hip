@@ -43,21 +43,14 @@
 //                  out-of-range access;
 //   sentence end   the final scores add alpha * lm(</s> | h(l)) (eos) and a W-element rank count writes the slot
 //                  permutation beam_backtrace follows (null: identity, the no-LM order).
-#include "cfm_common.h"
+#include "ctc_common.h"
 
-#include <math.h>
+using namespace ctc;
 
 namespace {
 
-constexpr float NEG_INF = -INFINITY;
 constexpr int BEAM_MAX = 128;
 constexpr int BT_LDS = 4096;   // back-pointer entries per LDS chunk of the backtrace
-
-__device__ __forceinline__ float lse2(float a, float b) {
-  const float m = fmaxf(a, b);
-  if (m == NEG_INF) return NEG_INF;
-  return m + logf(expf(a - m) + expf(b - m));
-}
 
 // ------------------------------------------------------------------------------------------ n-gram tables
 struct LmP {
@@ -111,10 +104,6 @@ __device__ __forceinline__ void lm_context(const LmP& lm, int u, int v, float& b
   const float2 g = lm.uni[cv];
   bo1 = lm.order >= 2 ? g.y : 0.f;
   bo2 = (lm.order >= 3 && u >= 0 && d.hit) ? d.bo : 0.f;
-}
-
-__device__ __forceinline__ int clamp_len(const int32_t* lens, int b, int T) {
-  return lens ? min(max(lens[b], 0), T) : T;
 }
 
 // ------------------------------------------------------------------------------------------ top-k per row
@@ -543,130 +532,155 @@ __global__ __launch_bounds__(64) void beam_backtrace(const int32_t* __restrict__
   }
 }
 
-size_t beam_ws_floats(int B, int T, int W) {
+// the workspace, as byte offsets: both *_ws_bytes functions and run_beam read this.  KP: stride of the token lists
+// (W + 1 without an LM, K with one); the LM search adds the slot permutation
+struct BeamWs { size_t row_lse, row_rb, tlp, tk, fin, perm, total; };
+BeamWs beam_ws(int B, int T, int W, int KP, bool lm) {
+  const size_t bt = (size_t)B * T, bw = (size_t)B * W;
+  BeamWs w;
+  w.row_lse = 0;
+  w.row_rb = w.row_lse + sizeof(float) * bt;
+  w.tlp = w.row_rb + sizeof(float) * bt;
+  w.tk = w.tlp + sizeof(float) * bt * KP;
+  w.fin = w.tk + sizeof(int32_t) * bt * KP;
+  w.perm = w.fin + sizeof(float) * bw;
+  w.total = w.perm + (lm ? sizeof(int32_t) * bw : 0);
+  return w;
+}
+
+// what both entry points hand to run_beam (fn names the entry point in messages), and what the LM one adds
+struct BeamArgs {
+  const char* fn;
+  const float* logits; long sb, st; const int32_t* lens;
+  int B, T, V, blank, pad, beam, nbest;
+  int32_t* bp_parent; int32_t* bp_token; int32_t* tokens; int32_t* out_len; float* score;
+  void* ws; void* stream;
+};
+// the shared arguments in the entry points' own order, each stored under its name
+BeamArgs beam_args(const char* fn, const float* logits, long sb, long st, const int32_t* lens, int B, int T, int V,
+                   int blank, int pad, int beam, int nbest, int32_t* bp_parent, int32_t* bp_token, int32_t* tokens,
+                   int32_t* out_len, float* score, void* ws, void* stream) {
+  BeamArgs a;
+  a.fn = fn; a.logits = logits; a.sb = sb; a.st = st; a.lens = lens;
+  a.B = B; a.T = T; a.V = V; a.blank = blank; a.pad = pad; a.beam = beam; a.nbest = nbest;
+  a.bp_parent = bp_parent; a.bp_token = bp_token; a.tokens = tokens; a.out_len = out_len; a.score = score;
+  a.ws = ws; a.stream = stream;
+  return a;
+}
+struct BeamLmArgs { const cfm_ngram_lm* lm; int token_beam; float alpha, beta; int eos; };
+
+// the three launches of either search; la null: the plain search
+int run_beam(const BeamArgs& a, const BeamLmArgs* la) {
+  const cfm_ngram_lm* lm = la ? la->lm : nullptr;
+  const int B = a.B, T = a.T, V = a.V, W = a.beam;
+  CFM_REQUIRE_FN(a.fn, a.logits && a.bp_parent && a.bp_token && a.tokens && a.out_len && a.score && a.ws, CFM_ERR_ARG,
+                 "null pointer");
+  CFM_REQUIRE_FN(a.fn, B > 0 && T > 0, CFM_ERR_SHAPE, "bad shape");
+  CFM_REQUIRE_FN(a.fn, V >= 2 && V <= 16384, CFM_ERR_UNSUPPORTED, "2 <= V <= 16384");
+  CFM_REQUIRE_FN(a.fn, W >= 1 && a.nbest >= 1 && a.nbest <= W, CFM_ERR_ARG, "1 <= nbest <= beam");
+  CFM_REQUIRE_FN(a.fn, W <= BEAM_MAX, CFM_ERR_UNSUPPORTED, "beam width must be <= 128");
+  CFM_REQUIRE_FN(a.fn, a.blank >= 0 && a.blank < V, CFM_ERR_ARG, "blank out of range");
+  CFM_REQUIRE_FN(a.fn, a.pad < V, CFM_ERR_ARG, "pad out of range");
+  // K tokens per frame, listed with stride KP.  Without an LM the pair rule needs the W + 1 best; with one every
+  // entry is extended by the token_beam best
+  const int ntok = V - 1 - ((a.pad >= 0 && a.pad != a.blank) ? 1 : 0);
+  const int want = lm ? la->token_beam : W + 1;
+  const int K = ntok < want ? ntok : want;
+  const int KP = lm ? K : W + 1;
+  if (lm) {
+    CFM_REQUIRE_FN(a.fn, K >= 1, CFM_ERR_UNSUPPORTED, "no token left to emit");
+    CFM_REQUIRE_FN(a.fn, W + W * K <= 1024, CFM_ERR_UNSUPPORTED, "beam + beam * token_beam must be <= 1024");
+    CFM_REQUIRE_FN(a.fn, K <= 768, CFM_ERR_UNSUPPORTED, "token_beam must be <= 768");
+  }
+  hipStream_t s = cfm::as_stream(a.stream);
   const size_t bt = (size_t)B * T;
-  return bt * (2 + 2 * (size_t)(W + 1)) + (size_t)B * W;
+  const BeamWs w = beam_ws(B, T, W, KP, lm != nullptr);
+  char* base = static_cast<char*>(a.ws);
+  float* row_lse = reinterpret_cast<float*>(base + w.row_lse);
+  float* row_rb = reinterpret_cast<float*>(base + w.row_rb);
+  float* tlp = reinterpret_cast<float*>(base + w.tlp);
+  int32_t* tk = reinterpret_cast<int32_t*>(base + w.tk);
+  float* fin = reinterpret_cast<float*>(base + w.fin);
+  int32_t* perm = lm ? reinterpret_cast<int32_t*>(base + w.perm) : nullptr;
+
+  const int wpb = V <= 4096 ? 4 : 1;
+  hipLaunchKernelGGL(beam_topk, dim3((unsigned)((bt + wpb - 1) / wpb)), dim3(64 * wpb),
+                     (size_t)wpb * V * sizeof(float), s, a.logits, a.sb, a.st, a.lens, B, T, V, a.blank,
+                     a.pad < 0 ? -1 : a.pad, K, KP, row_lse, row_rb, tk, tlp);
+
+  BeamP p;
+  p.x = a.logits; p.sb = a.sb; p.st = a.st; p.lens = a.lens;
+  p.B = B; p.T = T; p.V = V; p.W = W; p.K = K; p.KP = KP;
+  p.row_lse = row_lse; p.row_rb = row_rb; p.tk = tk; p.tlp = tlp;
+  p.bp_parent = a.bp_parent; p.bp_token = a.bp_token; p.fin = fin; p.perm = perm;
+  p.lm = LmP{};
+  // the LDS layout of beam_search: the arrays both searches have, then owner (plain) or prev, lt, bo2, bo1, clt (LM)
+  size_t sh;
+  unsigned block;
+  if (lm) {
+    p.NE = W * K;
+    p.NC = W + p.NE;
+    p.NP = (p.NC + 15) & ~15;   // the rank counting reads 16 keys per trip; padding costs candidates^2 work
+    p.lm.uni = static_cast<const float2*>(lm->unigrams);
+    p.lm.tab = static_cast<const uint4*>(lm->table);
+    p.lm.seed = lm->seed; p.lm.mask = lm->mask; p.lm.probe = lm->probe; p.lm.order = lm->order; p.lm.V = V;
+    p.lm.alpha = la->alpha; p.lm.beta = la->beta; p.lm.eos = la->eos ? 1 : 0;
+    sh = sizeof(int) * (2 * (size_t)W) + sizeof(float) * (4 * (size_t)W + p.NE);
+    block = (p.NP <= 128 && K <= 192) ? 64 : 256;   // the next frame's token list is prefetched three per thread
+  } else {
+    int ne = 0;
+    for (int i = 0; i < W; ++i) ne += ext_count(i, W, K);
+    p.NE = ne;
+    p.NC = W + ne;
+    int np = 16;
+    while (np < p.NC) np <<= 1;
+    p.NP = np;
+    sh = sizeof(int) * (size_t)(ne > 0 ? ne : 1);
+    block = np <= 128 ? 64 : 256;
+  }
+  sh += sizeof(uint64_t) * ((size_t)p.NP + 4 * W) + sizeof(float) * (3 * (size_t)p.NP + 7 * W + 2 * KP) +
+        sizeof(int) * (2 * (size_t)KP + 7 * W);
+  CFM_REQUIRE_FN(a.fn, sh <= 64 * 1024, CFM_ERR_UNSUPPORTED, "beam state exceeds the LDS budget");
+  if (lm) hipLaunchKernelGGL(beam_search<true>, dim3(B), dim3(block), sh, s, p);
+  else hipLaunchKernelGGL(beam_search<false>, dim3(B), dim3(block), sh, s, p);
+  hipLaunchKernelGGL(beam_backtrace, dim3(B), dim3(64), 0, s, a.bp_parent, a.bp_token, a.lens, fin,
+                     static_cast<const int32_t*>(perm), B, T, W, a.nbest, a.tokens, a.out_len, a.score);
+  return cfm::check_launch(a.fn);
 }
 
 }  // namespace
 
 CFM_EXPORT size_t cfm_ctc_beam_ws_bytes(int B, int T, int W) {
   if (B <= 0 || T <= 0 || W <= 0) return 0;
-  return sizeof(float) * beam_ws_floats(B, T, W);
+  return beam_ws(B, T, W, W + 1, false).total;
 }
 
 CFM_EXPORT int cfm_ctc_beam_decode(const float* logits, long sb, long st, const int32_t* lens, int B, int T, int V,
                                    int blank, int pad, int beam, int nbest, int32_t* bp_parent, int32_t* bp_token,
                                    int32_t* tokens, int32_t* out_len, float* score, void* ws, void* stream) {
-  CFM_REQUIRE(logits && bp_parent && bp_token && tokens && out_len && score && ws, CFM_ERR_ARG, "null pointer");
-  CFM_REQUIRE(B > 0 && T > 0, CFM_ERR_SHAPE, "bad shape");
-  CFM_REQUIRE(V >= 2 && V <= 16384, CFM_ERR_UNSUPPORTED, "2 <= V <= 16384");
-  CFM_REQUIRE(beam >= 1 && nbest >= 1 && nbest <= beam, CFM_ERR_ARG, "1 <= nbest <= beam");
-  CFM_REQUIRE(beam <= BEAM_MAX, CFM_ERR_UNSUPPORTED, "beam width must be <= 128");
-  CFM_REQUIRE(blank >= 0 && blank < V, CFM_ERR_ARG, "blank out of range");
-  CFM_REQUIRE(pad < V, CFM_ERR_ARG, "pad out of range");
-  hipStream_t s = cfm::as_stream(stream);
-  const int W = beam, KP = W + 1;
-  const int ntok = V - 1 - ((pad >= 0 && pad != blank) ? 1 : 0);
-  const int K = ntok < KP ? ntok : KP;
-  const size_t bt = (size_t)B * T;
-  float* row_lse = static_cast<float*>(ws);
-  float* row_rb = row_lse + bt;
-  float* tlp = row_rb + bt;
-  int32_t* tk = reinterpret_cast<int32_t*>(tlp + bt * KP);
-  float* fin = reinterpret_cast<float*>(tk + bt * KP);
-
-  const int wpb = V <= 4096 ? 4 : 1;
-  hipLaunchKernelGGL(beam_topk, dim3((unsigned)((bt + wpb - 1) / wpb)), dim3(64 * wpb),
-                     (size_t)wpb * V * sizeof(float), s, logits, sb, st, lens, B, T, V, blank, pad < 0 ? -1 : pad, K, KP, row_lse, row_rb, tk, tlp);
-
-  BeamP p;
-  p.x = logits; p.sb = sb; p.st = st; p.lens = lens;
-  p.B = B; p.T = T; p.V = V; p.W = W; p.K = K; p.KP = KP;
-  int ne = 0;
-  for (int i = 0; i < W; ++i) ne += ext_count(i, W, K);
-  p.NE = ne;
-  p.NC = W + ne;
-  int np = 16;
-  while (np < p.NC) np <<= 1;
-  p.NP = np;
-  p.row_lse = row_lse; p.row_rb = row_rb; p.tk = tk; p.tlp = tlp;
-  p.bp_parent = bp_parent; p.bp_token = bp_token; p.fin = fin;
-  p.perm = nullptr; p.lm = LmP{};
-  const size_t sh = sizeof(uint64_t) * ((size_t)np + 4 * W) +
-                    sizeof(float) * (3 * (size_t)np + 7 * W + 2 * KP) +
-                    sizeof(int) * (2 * (size_t)KP + 7 * W + (ne > 0 ? ne : 1));
-  CFM_REQUIRE(sh <= 64 * 1024, CFM_ERR_UNSUPPORTED, "beam state exceeds the LDS budget");
-  hipLaunchKernelGGL(beam_search<false>, dim3(B), dim3(np <= 128 ? 64 : 256), sh, s, p);
-  hipLaunchKernelGGL(beam_backtrace, dim3(B), dim3(64), 0, s, bp_parent, bp_token, lens, fin,
-                     static_cast<const int32_t*>(nullptr), B, T, W, nbest, tokens, out_len, score);
-  return cfm::check_launch("cfm_ctc_beam_decode");
+  return run_beam(beam_args(__func__, logits, sb, st, lens, B, T, V, blank, pad, beam, nbest, bp_parent, bp_token,
+                            tokens, out_len, score, ws, stream),
+                  nullptr);
 }
 
 CFM_EXPORT size_t cfm_ctc_beam_lm_ws_bytes(int B, int T, int W, int K) {
   if (B <= 0 || T <= 0 || W <= 0 || K <= 0) return 0;
-  const size_t bt = (size_t)B * T;
-  return sizeof(float) * (bt * (2 + 2 * (size_t)K) + 2 * (size_t)B * W);
+  return beam_ws(B, T, W, K, true).total;
 }
 
 CFM_EXPORT int cfm_ctc_beam_decode_lm(const float* logits, long sb, long st, const int32_t* lens, int B, int T, int V,
                                       int blank, int pad, int beam, int nbest, int token_beam, float alpha, float beta,
                                       int eos, const cfm_ngram_lm* lm, int32_t* bp_parent, int32_t* bp_token,
                                       int32_t* tokens, int32_t* out_len, float* score, void* ws, void* stream) {
-  CFM_REQUIRE(logits && bp_parent && bp_token && tokens && out_len && score && ws, CFM_ERR_ARG, "null pointer");
   CFM_REQUIRE(lm && lm->unigrams && lm->table, CFM_ERR_ARG, "null language-model table");
-  CFM_REQUIRE(B > 0 && T > 0, CFM_ERR_SHAPE, "bad shape");
-  CFM_REQUIRE(V >= 2 && V <= 16384, CFM_ERR_UNSUPPORTED, "2 <= V <= 16384");
-  CFM_REQUIRE(beam >= 1 && nbest >= 1 && nbest <= beam, CFM_ERR_ARG, "1 <= nbest <= beam");
-  CFM_REQUIRE(beam <= BEAM_MAX, CFM_ERR_UNSUPPORTED, "beam width must be <= 128");
-  CFM_REQUIRE(blank >= 0 && blank < V, CFM_ERR_ARG, "blank out of range");
-  CFM_REQUIRE(pad < V, CFM_ERR_ARG, "pad out of range");
   CFM_REQUIRE(token_beam >= 1, CFM_ERR_ARG, "token_beam must be >= 1");
   CFM_REQUIRE(lm->V == V, CFM_ERR_ARG, "the language model's V differs from the logits'");
   CFM_REQUIRE(lm->order >= 1 && lm->order <= 3, CFM_ERR_UNSUPPORTED, "n-gram order must be 1..3");
   CFM_REQUIRE(lm->probe >= 1 && lm->probe <= 4, CFM_ERR_UNSUPPORTED, "probe length must be 1..4");
   CFM_REQUIRE((lm->mask & (lm->mask + 1u)) == 0u, CFM_ERR_ARG, "table capacity must be a power of two");
-  hipStream_t s = cfm::as_stream(stream);
-  const int W = beam;
-  const int ntok = V - 1 - ((pad >= 0 && pad != blank) ? 1 : 0);
-  const int K = ntok < token_beam ? ntok : token_beam;
-  CFM_REQUIRE(K >= 1, CFM_ERR_UNSUPPORTED, "no token left to emit");
-  CFM_REQUIRE(W + W * K <= 1024, CFM_ERR_UNSUPPORTED, "beam + beam * token_beam must be <= 1024");
-  CFM_REQUIRE(K <= 768, CFM_ERR_UNSUPPORTED, "token_beam must be <= 768");
-  const size_t bt = (size_t)B * T;
-  float* row_lse = static_cast<float*>(ws);
-  float* row_rb = row_lse + bt;
-  float* tlp = row_rb + bt;
-  int32_t* tk = reinterpret_cast<int32_t*>(tlp + bt * K);
-  float* fin = reinterpret_cast<float*>(tk + bt * K);
-  int32_t* perm = reinterpret_cast<int32_t*>(fin + (size_t)B * W);
-
-  const int wpb = V <= 4096 ? 4 : 1;
-  hipLaunchKernelGGL(beam_topk, dim3((unsigned)((bt + wpb - 1) / wpb)), dim3(64 * wpb),
-                     (size_t)wpb * V * sizeof(float), s, logits, sb, st, lens, B, T, V, blank, pad < 0 ? -1 : pad, K, K, row_lse, row_rb, tk, tlp);
-
-  BeamP p;
-  p.x = logits; p.sb = sb; p.st = st; p.lens = lens;
-  p.B = B; p.T = T; p.V = V; p.W = W; p.K = K; p.KP = K;
-  p.NE = W * K;
-  p.NC = W + p.NE;
-  const int np = (p.NC + 15) & ~15;   // the rank counting reads 16 keys per trip; padding costs candidates^2 work
-  p.NP = np;
-  p.row_lse = row_lse; p.row_rb = row_rb; p.tk = tk; p.tlp = tlp;
-  p.bp_parent = bp_parent; p.bp_token = bp_token; p.fin = fin; p.perm = perm;
-  p.lm.uni = static_cast<const float2*>(lm->unigrams);
-  p.lm.tab = static_cast<const uint4*>(lm->table);
-  p.lm.seed = lm->seed; p.lm.mask = lm->mask; p.lm.probe = lm->probe; p.lm.order = lm->order; p.lm.V = V;
-  p.lm.alpha = alpha; p.lm.beta = beta; p.lm.eos = eos ? 1 : 0;
-  // the layout of beam_search: the no-LM arrays with owner left out, then prev, lt, bo2, bo1, clt
-  const size_t sh = sizeof(uint64_t) * ((size_t)np + 4 * W) +
-                    sizeof(float) * (3 * (size_t)np + 7 * W + 2 * K) +
-                    sizeof(int) * (2 * (size_t)K + 7 * W) +
-                    sizeof(int) * (2 * (size_t)W) + sizeof(float) * (4 * (size_t)W + p.NE);
-  CFM_REQUIRE(sh <= 64 * 1024, CFM_ERR_UNSUPPORTED, "beam state exceeds the LDS budget");
-  // the next frame's token list is prefetched three per thread
-  hipLaunchKernelGGL(beam_search<true>, dim3(B), dim3((np <= 128 && K <= 192) ? 64 : 256), sh, s, p);
-  hipLaunchKernelGGL(beam_backtrace, dim3(B), dim3(64), 0, s, bp_parent, bp_token, lens, fin,
-                     static_cast<const int32_t*>(perm), B, T, W, nbest, tokens, out_len, score);
-  return cfm::check_launch("cfm_ctc_beam_decode_lm");
+  BeamLmArgs la;
+  la.lm = lm; la.token_beam = token_beam; la.alpha = alpha; la.beta = beta; la.eos = eos;
+  return run_beam(beam_args(__func__, logits, sb, st, lens, B, T, V, blank, pad, beam, nbest, bp_parent, bp_token,
+                            tokens, out_len, score, ws, stream),
+                  &la);
 }

@@ -24,7 +24,7 @@
 //                      and counts hits / substitutions / deletions / insertions, all lanes in parallel.
 // Tie rule (part of the contract): the first of diagonal, up, left that attains the minimum; i == 0 walks left,
 // j == 0 walks up.
-#include "cfm_common.h"
+#include "ctc_common.h"
 
 namespace {
 
@@ -42,13 +42,9 @@ struct EdP {
 
 // lengths are device data, clamped to the buffers' extents: a bad value can give a wrong answer, never an access
 // outside ref / hyp / the workspace / the outputs
-__device__ __forceinline__ int ref_len_of(const EdP& p, int pair) {
-  return min(max(p.ref_len[pair / p.group], 0), p.Rmax);
-}
-__device__ __forceinline__ int hyp_len_of(const EdP& p, int pair) { return min(max(p.hyp_len[pair], 0), p.Hmax); }
-
-// lane l <- lane l - 1 (wave_shr:1; lane 0 receives 0 and is overwritten by the caller)
-__device__ __forceinline__ int shr1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xF, 0xF, true); }
+// (ctc_common.h's clamp; ref_len and hyp_len are never null: the entry point requires them)
+__device__ __forceinline__ int ref_len_of(const EdP& p, int pair) { return ctc::clamp0(p.ref_len[pair / p.group], p.Rmax); }
+__device__ __forceinline__ int hyp_len_of(const EdP& p, int pair) { return ctc::clamp0(p.hyp_len[pair], p.Hmax); }
 
 template <bool OPS>
 __global__ __launch_bounds__(64) void ed_recursion(EdP p, int32_t* __restrict__ dist) {
@@ -87,7 +83,7 @@ __global__ __launch_bounds__(64) void ed_recursion(EdP p, int32_t* __restrict__ 
       for (int q = 0; q < CH; ++q) {
         const int t = t0 + q;
         const int top_q = __builtin_amdgcn_readlane(top_c, q), tok_q = __builtin_amdgcn_readlane(tok_c, q);
-        const int cur_s = shr1(cur), tok_s = shr1(htok);   // all lanes take part in the shifts
+        const int cur_s = wave_shr1(cur), tok_s = wave_shr1(htok);   // all lanes take part in the shifts
         const int up = lane == 0 ? top_q : cur_s;
         htok = lane == 0 ? tok_q : tok_s;
         const int j = t - lane + 1;

@@ -72,6 +72,26 @@ def _prep_targets(targets, tgt_len, B, device):
     raise ValueError("targets must be (B, S) padded or 1-D concatenated")
 
 
+def _logits(x, batch_first, who, what="logits", need_3d=False):
+    """(x, B, T) of `who`'s logits argument: fp32 CUDA (RuntimeError naming `who`), optionally 3-D (ValueError), the
+    class dimension made contiguous."""
+    if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32:
+        raise RuntimeError(f"{who} runs on libcfm: fp32 CUDA {what} required")
+    if need_3d and x.dim() != 3:
+        raise ValueError("logits must be (B, T, V), or (T, B, V) with batch_first=False")
+    x = x if x.stride(-1) == 1 else x.contiguous()
+    B, T = (x.shape[0], x.shape[1]) if batch_first else (x.shape[1], x.shape[0])
+    return x, B, T
+
+
+def _problem(targets, in_len, tgt_len, B, T, device):
+    """(il, tl, tg, ldt, off, smax): the lengths as _lengths gives them (host-side ones validated against T and the
+    padded targets' width) and the targets as _prep_targets gives them."""
+    il = _lengths(in_len, B, device, T, "input_lengths")
+    tl = _lengths(tgt_len, B, device, targets.shape[1] if targets.dim() == 2 else None, "target_lengths")
+    return (il, tl) + _prep_targets(targets, tl, B, device)
+
+
 _NONFINITE = None
 
 
@@ -96,15 +116,9 @@ def _reduce(nll, tl, reduction):
 class _CTCFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, targets, in_len, tgt_len, blank, reduction, zero_infinity, batch_first):
-        if not x.is_cuda or x.dtype != torch.float32:
-            raise RuntimeError("ctc_loss runs on libcfm: fp32 CUDA log-probs/logits required")
-        x = x if x.stride(-1) == 1 else x.contiguous()
-        B = x.shape[0] if batch_first else x.shape[1]
-        T = x.shape[1] if batch_first else x.shape[0]
+        x, B, T = _logits(x, batch_first, "ctc_loss", "log-probs/logits")
         _check_blank(blank, x.shape[-1])
-        il = _lengths(in_len, B, x.device, T, "input_lengths")
-        tl = _lengths(tgt_len, B, x.device, targets.shape[1] if targets.dim() == 2 else None, "target_lengths")
-        tg, ldt, off, smax = _prep_targets(targets, tl, B, x.device)
+        il, tl, tg, ldt, off, smax = _problem(targets, in_len, tgt_len, B, T, x.device)
         nll, ws = ops.ctc_loss_fwd(x, tg, ldt, off, il, tl, smax, blank, zero_infinity, batch_first)
         ctx.save_for_backward(x, tg, off if off is not None else tg, il, tl, ws)
         ctx.cfg = (ldt, off is not None, smax, blank, zero_infinity, batch_first, reduction)
@@ -151,9 +165,7 @@ class _CTCHeadFn(torch.autograd.Function):
         wc = w if w.dtype == cd else ops.cast(w, cd)
         logits = ops.linear(yc, wc, b, out_dtype=torch.float32).view(B, T, -1)
         _check_blank(blank, w.shape[0])
-        il = _lengths(in_len, B, y.device, T, "input_lengths")
-        tl = _lengths(tgt_len, B, y.device, targets.shape[1] if targets.dim() == 2 else None, "target_lengths")
-        tg, ldt, off, smax = _prep_targets(targets, tl, B, y.device)
+        il, tl, tg, ldt, off, smax = _problem(targets, in_len, tgt_len, B, T, y.device)
         nll, ws = ops.ctc_loss_fwd(logits, tg, ldt, off, il, tl, smax, blank, zero_infinity, True)
         ctx.save_for_backward(logits, yc, wc, tg, off if off is not None else tg, il, tl, ws)
         ctx.cfg = (ldt, off is not None, smax, blank, zero_infinity, reduction, cd, y.dtype, b is not None)
@@ -188,10 +200,7 @@ def greedy_decode(logits, lengths=None, blank=0, pad=-1, collapse=False, batch_f
     """ASRNN.predict + Vocab.decode's id filter on the device.
     Returns (ids (B, T) int64 = torch.argmax(logits, -1), tokens (B, T) int32 padded with -1, n (B,));
     compact=False: ids only (tokens, n are None)."""
-    if not logits.is_cuda or logits.dtype != torch.float32:
-        raise RuntimeError("greedy_decode runs on libcfm: fp32 CUDA logits required")
-    x = logits if logits.stride(-1) == 1 else logits.contiguous()
-    B = x.shape[0] if batch_first else x.shape[1]
+    x, B, _ = _logits(logits, batch_first, "greedy_decode")
     ln = None if lengths is None else _lengths(lengths, B, x.device)
     return ops.ctc_greedy_decode(x, ln, blank, pad, collapse, batch_first, compact)
 
@@ -222,16 +231,11 @@ def beam_search_decode(logits, lengths=None, beam_size=16, blank=0, pad=-1, nbes
         raise ValueError(f"beam_size must be an integer in [1, {BEAM_MAX}], got {beam_size!r}")
     if not isinstance(nbest, int) or isinstance(nbest, bool) or not 1 <= nbest <= beam_size:
         raise ValueError(f"nbest must be an integer in [1, beam_size], got {nbest!r}")
-    if not logits.is_cuda or logits.dtype != torch.float32:
-        raise RuntimeError("beam_search_decode runs on libcfm: fp32 CUDA logits required")
-    if logits.dim() != 3:
-        raise ValueError("logits must be (B, T, V), or (T, B, V) with batch_first=False")
-    V = logits.shape[-1]
+    x, B, _ = _logits(logits, batch_first, "beam_search_decode", need_3d=True)
+    V = x.shape[-1]
     _check_blank(blank, V)
     if pad >= V:
         raise ValueError(f"pad must be in label range [0, {V}) or negative, got {pad}")
-    x = logits if logits.stride(-1) == 1 else logits.contiguous()
-    B = x.shape[0] if batch_first else x.shape[1]
     ln = None if lengths is None else _lengths(lengths, B, x.device)
     if lm is None:
         if lm_weight != 0.0 or word_bonus != 0.0 or token_beam is not None or lm_eos is not True:
@@ -284,13 +288,7 @@ def forced_align(logits, targets, input_lengths=None, target_lengths=None, blank
     Infeasible utterances (fewer frames than labels plus adjacent equal label pairs, so also no frames but labels;
     or a best path whose score is not finite): score -inf, alignments -1, scores 0, spans -1 / -1 / 0.  No frames
     and no labels: score 0.  No labels: every frame blank."""
-    if not torch.is_tensor(logits) or not logits.is_cuda or logits.dtype != torch.float32:
-        raise RuntimeError("forced_align runs on libcfm: fp32 CUDA logits required")
-    if logits.dim() != 3:
-        raise ValueError("logits must be (B, T, V), or (T, B, V) with batch_first=False")
-    x = logits if logits.stride(-1) == 1 else logits.contiguous()
-    B = x.shape[0] if batch_first else x.shape[1]
-    T = x.shape[1] if batch_first else x.shape[0]
+    x, B, T = _logits(logits, batch_first, "forced_align", need_3d=True)
     blank = int(blank)
     _check_blank(blank, x.shape[-1])
     if not torch.is_tensor(targets):
@@ -308,8 +306,7 @@ def forced_align(logits, targets, input_lengths=None, target_lengths=None, blank
         host_tl = None if target_lengths.is_cuda else target_lengths.tolist()
     else:
         host_tl = list(target_lengths)
-    il = _lengths(input_lengths, B, x.device, T, "input_lengths")
-    tl = _lengths(target_lengths, B, x.device, targets.shape[1] if targets.dim() == 2 else None, "target_lengths")
+    il, tl, tg, ldt, off, smax = _problem(targets, input_lengths, target_lengths, B, T, x.device)
     if not targets.is_cuda and host_tl is not None:
         rows = targets.tolist()
         if targets.dim() == 2:
@@ -318,7 +315,6 @@ def forced_align(logits, targets, input_lengths=None, target_lengths=None, blank
             bad = blank in rows[:sum(host_tl)]
         if bad:
             raise ValueError(f"targets must not contain the blank index {blank}")
-    tg, ldt, off, smax = _prep_targets(targets, tl, B, x.device)
     if smax > ALIGN_MAX_LABELS:
         raise ValueError(f"forced_align takes at most {ALIGN_MAX_LABELS} labels per utterance, got {smax}")
     return ForcedAlignment(*ops.ctc_forced_align(x, tg, ldt, off, il, tl, smax, blank, batch_first))

@@ -1094,21 +1094,26 @@ def ctc_greedy_decode(x, lengths_i32=None, blank=0, pad=-1, collapse=False, batc
     return ids, out, out_len
 
 
-def ctc_beam_decode(x, lengths_i32=None, beam=16, blank=0, pad=-1, nbest=1, batch_first=True):
-    """CTC prefix beam search (cfm_ctc_beam_decode) -> tokens (B, nbest, T) int32 padded with -1, lengths (B, nbest)
-    int32, scores (B, nbest) fp32, and the back-pointer table bp_parent / bp_token (B, T, beam) int32."""
-    B, T, sb, st = _rows(x, batch_first)
-    dev = x.device
+def _beam_outputs(B, T, beam, nbest, dev):
+    """(tokens, out_len, score, bp_parent, bp_token) of either beam search, uninitialised."""
     bp_parent = torch.empty(B, T, beam, device=dev, dtype=torch.int32)
     bp_token = torch.empty(B, T, beam, device=dev, dtype=torch.int32)
     tokens = torch.empty(B, nbest, T, device=dev, dtype=torch.int32)
     out_len = torch.empty(B, nbest, device=dev, dtype=torch.int32)
     score = torch.empty(B, nbest, device=dev, dtype=torch.float32)
-    ws = workspace(L.size_call("cfm_ctc_beam_ws_bytes", B, T, int(beam)), dev)
+    return tokens, out_len, score, bp_parent, bp_token
+
+
+def ctc_beam_decode(x, lengths_i32=None, beam=16, blank=0, pad=-1, nbest=1, batch_first=True):
+    """CTC prefix beam search (cfm_ctc_beam_decode) -> tokens (B, nbest, T) int32 padded with -1, lengths (B, nbest)
+    int32, scores (B, nbest) fp32, and the back-pointer table bp_parent / bp_token (B, T, beam) int32."""
+    B, T, sb, st = _rows(x, batch_first)
+    out = tokens, out_len, score, bp_parent, bp_token = _beam_outputs(B, T, beam, nbest, x.device)
+    ws = workspace(L.size_call("cfm_ctc_beam_ws_bytes", B, T, int(beam)), x.device)
     L.call("cfm_ctc_beam_decode", L.ptr(x), sb, st, L.ptr(lengths_i32), B, T, x.shape[-1], int(blank), int(pad),
            int(beam), int(nbest), L.ptr(bp_parent), L.ptr(bp_token), L.ptr(tokens), L.ptr(out_len), L.ptr(score),
            L.ptr(ws), L.stream())
-    return tokens, out_len, score, bp_parent, bp_token
+    return out
 
 
 def ctc_beam_decode_lm(x, lm_tables, lengths_i32=None, beam=16, token_beam=17, lm_weight=0.0, word_bonus=0.0,
@@ -1117,20 +1122,15 @@ def ctc_beam_decode_lm(x, lm_tables, lengths_i32=None, beam=16, token_beam=17, l
     NGramLM.device_tables(x.device).  token_beam: already clamped to the number of tokens that can be emitted.
     Returns what ctc_beam_decode returns; the scores are fused scores."""
     B, T, sb, st = _rows(x, batch_first)
-    dev = x.device
-    bp_parent = torch.empty(B, T, beam, device=dev, dtype=torch.int32)
-    bp_token = torch.empty(B, T, beam, device=dev, dtype=torch.int32)
-    tokens = torch.empty(B, nbest, T, device=dev, dtype=torch.int32)
-    out_len = torch.empty(B, nbest, device=dev, dtype=torch.int32)
-    score = torch.empty(B, nbest, device=dev, dtype=torch.float32)
-    ws = workspace(L.size_call("cfm_ctc_beam_lm_ws_bytes", B, T, int(beam), int(token_beam)), dev)
+    out = tokens, out_len, score, bp_parent, bp_token = _beam_outputs(B, T, beam, nbest, x.device)
+    ws = workspace(L.size_call("cfm_ctc_beam_lm_ws_bytes", B, T, int(beam), int(token_beam)), x.device)
     desc = L.NGramLMDesc(L.ptr(lm_tables["uni"]), L.ptr(lm_tables["table"]), int(lm_tables["seed"]),
                          int(lm_tables["mask"]), int(lm_tables["probe"]), int(lm_tables["order"]), int(lm_tables["V"]))
     L.call("cfm_ctc_beam_decode_lm", L.ptr(x), sb, st, L.ptr(lengths_i32), B, T, x.shape[-1], int(blank), int(pad),
            int(beam), int(nbest), int(token_beam), float(lm_weight), float(word_bonus), int(bool(eos)),
            ctypes.byref(desc), L.ptr(bp_parent), L.ptr(bp_token), L.ptr(tokens), L.ptr(out_len), L.ptr(score),
            L.ptr(ws), L.stream())
-    return tokens, out_len, score, bp_parent, bp_token
+    return out
 
 
 def ctc_forced_align(x, targets_i32, ldt, tgt_off, in_len_i32, tgt_len_i32, smax, blank, batch_first=True):
