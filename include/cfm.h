@@ -944,6 +944,45 @@ int cfm_ctc_forced_align(const float* logits, long sb, long st, const int32_t* t
                          int Smax, int blank, int32_t* alignments, float* scores, float* score, int32_t* starts,
                          int32_t* ends, float* token_scores, void* ws, void* stream);
 
+/* CTC likelihood of an n-best list and the expected risk over it (MWER training, Prabhavalkar et al. 2018; n-best
+ * rescoring): N hypotheses per utterance against the utterance's ONE emission matrix.  The reference has no
+ * counterpart.  logits, sb / st, in_len, blank as cfm_ctc_loss_fwd (logits or log-probabilities: log-softmax is
+ * applied).  J = B * N problems, problem j = b * N + n: hypothesis row hyp + j * ldh (int32 ids), hyp_len[j] labels;
+ * hyp_len[j] < 0: the hypothesis is missing; hyp_len[j] > max_labels: it is left out the same way.  Lengths and ids
+ * are device data, clamped, never read back.  1 <= N <= 128 (CFM_ERR_ARG below, CFM_ERR_UNSUPPORTED above),
+ * max_labels <= min(ldh, 511) (CFM_ERR_SHAPE / CFM_ERR_UNSUPPORTED); hyp may be NULL when max_labels == 0.
+ *   ll (J) fp32     log P_ctc(y_j | x_b), natural log, over all alignments; -inf for an infeasible hypothesis
+ *                   (in_len[b] < L + adjacent equal labels, so also in_len 0 with L > 0), a result that is not finite,
+ *                   and a missing or over-long hypothesis; in_len 0 with L 0: 0
+ *   live            ll finite (hence present and within max_labels)
+ *   post (J) fp32   softmax of ll over the live n of the utterance; 0 elsewhere
+ *   loss (B) fp32   sum_n post * (risk - rbar), rbar the plain mean of risk (J, fp32) over the live n; 0 with fewer
+ *                   than two live hypotheses.  risk and loss: both or neither (NULL: ll and post only)
+ *   c = post * ((risk - rbar) - loss), sum_n c = 0; equal risks give c == 0 exactly (rbar is formed in double)
+ * cfm_ctc_nbest_bwd after cfm_ctc_nbest_fwd with risk, same arguments and the same ws untouched in between:
+ *   grad_logits[b, t, v] (fp32, row (b, t) at b*gsb + t*gst, every row written whole)
+ *     = grad_loss[b * grad_stride] * sum_n c[b, n] * occ_n[t, v]   for t < in_len[b]
+ * with occ_n[t, v] the posterior probability that hypothesis n's alignment emits class v at frame t
+ * (exp(alpha + beta - lpe - ll) summed over the states of class v).  d ll / d logits = occ - softmax(logits); the
+ * softmax term is multiplied by sum_n c = 0 and is never formed.  Exactly 0: frames t >= in_len[b], classes that are
+ * neither the blank nor a label of a hypothesis with c != 0, utterances with fewer than two live hypotheses or equal
+ * risks.  grad_stride 1, or 0 for one scalar.
+ * The recursions keep alpha, beta and ll in double and take their exponentials and logarithms in fp32 on O(1)
+ * differences, so a frame's error does not grow with |log p| (csrc/ctc_nbest.hip, "Precision").
+ * ws: cfm_ctc_nbest_ws_bytes(B, T, N, max_labels), 8-byte aligned (CFM_ERR_ALIGN): per (j, t, state) one double of
+ * alpha and one float that holds the emission after the forward and the occupancy after the backward, J * T *
+ * (2 max_labels + 1) cells in all.  Forward: three launches (emissions with the row statistics once per (b, t) row, alpha, weights); backward:
+ * two (beta / occupancy, gradient rows).  No host synchronisation (graph-capturable), no wait on another wave's
+ * progress anywhere, no floating-point atomics: every sum runs in an order fixed by the inputs (n order, then state
+ * order), so results are bit-identical from run to run. */
+size_t cfm_ctc_nbest_ws_bytes(int B, int T, int N, int max_labels);
+int cfm_ctc_nbest_fwd(const float* logits, long sb, long st, const int32_t* in_len, int B, int T, int V,
+                      const int32_t* hyp, int ldh, const int32_t* hyp_len, int N, int max_labels, int blank,
+                      const float* risk, float* ll, float* post, float* loss, void* ws, void* stream);
+int cfm_ctc_nbest_bwd(const float* logits, long sb, long st, const int32_t* in_len, int B, int T, int V,
+                      const int32_t* hyp, int ldh, const int32_t* hyp_len, int N, int max_labels, int blank, void* ws,
+                      const float* grad_loss, int grad_stride, float* grad_logits, long gsb, long gst, void* stream);
+
 /* Batched edit distance (Levenshtein) over token ids: the numerator of the word error rate -- the vocabulary's tokens
  * are words -- in place of the host loop of jiwer's wer (reference runner.py:160,230), and the aligned pairs the
  * reference's confusion matrix is built from (evals.py:64).  Pair p < P compares hypothesis row p (hyp + p * ldh,

@@ -327,6 +327,14 @@ _SIGS = {
     "cfm_ctc_forced_align": (c_int, [c_void_p, c_long, c_long, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                      c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p]),
+    "cfm_ctc_nbest_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),   # (B, T, N, max_labels)
+    # (logits, sb, st, in_len, B, T, V, hyp, ldh, hyp_len, N, max_labels, blank, risk, ll, post, loss, ws, stream)
+    "cfm_ctc_nbest_fwd": (c_int, [c_void_p, c_long, c_long, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                                  c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # (the same through blank, ws, grad_loss, grad_stride, grad_logits, gsb, gst, stream)
+    "cfm_ctc_nbest_bwd": (c_int, [c_void_p, c_long, c_long, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                                  c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_long, c_long,
+                                  c_void_p]),
     "cfm_edit_distance_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),   # (P, Rmax, Hmax, want_ops)
     # (ref, ldr, ref_len, n_ref, hyp, ldh, hyp_len, P, group, Rmax, Hmax, dist, counts, pair_ref, pair_hyp, ldp,
     #  n_pairs, ws, stream)

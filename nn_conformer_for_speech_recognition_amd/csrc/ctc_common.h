@@ -1,4 +1,4 @@
-// ctc_common.h — what the CTC-side kernels share (ctc.hip, ctc_align.hip, ctc_beam.hip, edit_distance.hip): the
+// ctc_common.h — what the CTC-side kernels share (ctc.hip, ctc_align.hip, ctc_beam.hip, ctc_nbest.hip, edit_distance.hip): the
 // problem view with its clamped accessors, the emission prep's row sweep, the lpe prefetch of the recursions, and
 // the host-side argument check.  A new CTC-side kernel includes this, derives its parameter struct from CtcView
 // and adds no clamp of its own ("CTC family: the shared header").
@@ -58,15 +58,10 @@ __device__ __forceinline__ int ext_label(const CtcView& p, const int32_t* tg, in
 // then lpe[row, st] = emit(logit of the st-th extended label, m, log s) for the utterance's states; with lse_out the
 // row's m + log s is stored too.  The two callers differ in emit alone (their roundings differ on purpose).
 // beam_topk has a sweep of its own: it stages the row in LDS and sums in double.
-template <typename Emit>
-__device__ __forceinline__ void prep_row(const CtcView& p, float* lpe, float* lse_out, Emit emit) {
-  const int lane = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= (long)p.B * p.T) return;
-  const int b = (int)(row / p.T), t = (int)(row % p.T);
-  if (t >= in_len_of(p, b)) return;
-  const float* x = p.logits + b * p.sb + t * p.st;
-  float m = NEG_INF;
+// row_stats is the sweep alone (m and ls = log s of the row at x, the whole wave taking part), for a caller that
+// writes the emissions of several label sequences from one sweep (ctc_nbest.hip).
+__device__ __forceinline__ void row_stats(const CtcView& p, const float* x, int lane, float& m, float& ls) {
+  m = NEG_INF;
   const bool v4 = (p.V % 4 == 0) && (p.sb % 4 == 0) && (p.st % 4 == 0) && ((uintptr_t)p.logits % 16 == 0);
   if (v4) {
     for (int v = lane * 4; v < p.V; v += 256) {
@@ -87,7 +82,19 @@ __device__ __forceinline__ void prep_row(const CtcView& p, float* lpe, float* ls
     for (int v = lane; v < p.V; v += 64) s += expf(x[v] - m);
   }
   s = wave_sum(s);
-  const float ls = logf(s);
+  ls = logf(s);
+}
+
+template <typename Emit>
+__device__ __forceinline__ void prep_row(const CtcView& p, float* lpe, float* lse_out, Emit emit) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= (long)p.B * p.T) return;
+  const int b = (int)(row / p.T), t = (int)(row % p.T);
+  if (t >= in_len_of(p, b)) return;
+  const float* x = p.logits + b * p.sb + t * p.st;
+  float m, ls;
+  row_stats(p, x, lane, m, ls);
   if (lse_out && lane == 0) lse_out[row] = m + ls;
   const int Sb = 2 * tgt_len_of(p, b) + 1;
   const int32_t* tg = tgt_of(p, b);

@@ -399,3 +399,125 @@ def edit_distance(hyp, ref, hyp_lengths=None, ref_lengths=None, ops=False):
         return EditDistance(dist.view(lead), rl, None, None, None, None)
     return EditDistance(dist.view(lead), rl, counts.view(lead + (4,)), pair_ref.view(lead + (Lr + Lh,)),
                         pair_hyp.view(lead + (Lr + Lh,)), n_pairs.view(lead))
+
+
+ExpectedRisk = namedtuple("ExpectedRisk", "loss ll post")
+NBEST_MAX = 128
+NBEST_MAX_LABELS = 511
+
+
+def _nbest_problem(logits, hyps, hyp_lengths, input_lengths, blank, batch_first, max_labels, who):
+    """(x, il, hyp rows int32, ldh, hl (B*N,) int32, N, max_labels) of an n-best call."""
+    x, B, T = _logits(logits, batch_first, who, need_3d=True)
+    _check_blank(blank, x.shape[-1])
+    if not torch.is_tensor(hyps) or not hyps.is_cuda:
+        raise RuntimeError(f"{who} runs on libcfm: CUDA id tensors required")
+    if hyps.dim() != 3 or hyps.shape[0] != B:
+        raise ValueError(f"hyps must be (B, N, L) with B = {B}, got {tuple(hyps.shape)}")
+    N, Lh = hyps.shape[1], hyps.shape[2]
+    if not 1 <= N <= NBEST_MAX:
+        raise ValueError(f"N must be in [1, {NBEST_MAX}], got {N}")
+    if max_labels is None:
+        max_labels = min(Lh, NBEST_MAX_LABELS)
+    max_labels = int(max_labels)
+    if not 0 <= max_labels <= min(Lh, NBEST_MAX_LABELS):
+        raise ValueError(f"max_labels must be in [0, min(L, {NBEST_MAX_LABELS})] = [0, {min(Lh, NBEST_MAX_LABELS)}], "
+                         f"got {max_labels}")
+    h2, ldh = _id_rows(hyps.reshape(B * N, Lh), "hyps")
+    if hyp_lengths is None:
+        hl = torch.full((B * N,), Lh, dtype=torch.int32, device=x.device)
+    else:
+        if isinstance(hyp_lengths, (list, tuple)):
+            hyp_lengths = torch.tensor(hyp_lengths)
+        if not torch.is_tensor(hyp_lengths) or hyp_lengths.numel() != B * N:
+            raise ValueError(f"hyp_lengths must hold (B, N) = ({B}, {N}) lengths (negative: a missing hypothesis)")
+        if not hyp_lengths.is_cuda and hyp_lengths.numel() > 0 and int(hyp_lengths.max()) > Lh:
+            raise ValueError(f"expected hyp_lengths to have value at most {Lh}, but got value {int(hyp_lengths.max())}")
+        hl = hyp_lengths.to(device=x.device, dtype=torch.int32).reshape(-1).contiguous()
+    if input_lengths is None:
+        il = torch.full((B,), T, dtype=torch.int32, device=x.device)
+    else:
+        il = _lengths(input_lengths, B, x.device, T, "input_lengths")
+    return x, il, h2, ldh, hl, N, max_labels
+
+
+def nbest_log_likelihood(logits, hyps, hyp_lengths=None, input_lengths=None, blank=0, batch_first=True,
+                         max_labels=None):
+    """Full CTC log-likelihood of each hypothesis of an n-best list (cfm_ctc_nbest_fwd): rescoring the beam's n-best,
+    whose own scores sum only the alignments the beam kept.  logits (B, T, V) fp32 CUDA (or (T, B, V) with
+    batch_first=False), raw or log-probabilities; hyps (B, N, L) int32 / int64 CUDA ids, e.g. beam_search_decode's
+    tokens; hyp_lengths (B, N) device tensor, host list or None (L), a negative length marks a missing hypothesis;
+    input_lengths as for forced_align.  Device lengths and ids are clamped, never read back.  1 <= N <= 128; at most
+    max_labels (None: min(L, 511)) labels per hypothesis, longer ones are left out like missing ones.
+    Returns (ll (B, N), post (B, N)) fp32, no gradient: ll = log P_ctc(hypothesis | logits) over all alignments (-inf
+    where infeasible, not finite, missing or too long), post = softmax of ll over the utterance's finite entries."""
+    blank = int(blank)
+    x, il, h2, ldh, hl, N, ml = _nbest_problem(logits, hyps, hyp_lengths, input_lengths, blank, batch_first, max_labels,
+                                               "nbest_log_likelihood")
+    with torch.no_grad():
+        ll, post, _, _ = ops.ctc_nbest_fwd(x.detach(), il, h2, ldh, hl, N, ml, blank, None, batch_first)
+    return ll, post
+
+
+class _ExpectedRiskFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, il, h2, ldh, hl, N, ml, blank, risk, batch_first):
+        ll, post, loss, ws = ops.ctc_nbest_fwd(x, il, h2, ldh, hl, N, ml, blank, risk, batch_first)
+        ctx.save_for_backward(x, il, h2, hl, ws)
+        ctx.cfg = (ldh, N, ml, blank, batch_first)
+        ctx.mark_non_differentiable(ll, post)
+        return loss, ll, post
+
+    @staticmethod
+    def backward(ctx, g, _gll, _gpost):
+        x, il, h2, hl, ws = ctx.saved_tensors
+        ldh, N, ml, blank, bf = ctx.cfg
+        dx = ops.ctc_nbest_bwd(x, il, h2, ldh, hl, N, ml, blank, ws, g, bf)
+        return dx, None, None, None, None, None, None, None, None, None
+
+
+def expected_risk_loss(logits, hyps, hyp_lengths, risk, input_lengths=None, blank=0, batch_first=True,
+                       max_labels=None):
+    """Expected risk over an n-best list (cfm_ctc_nbest_fwd / _bwd): the MWER criterion of Prabhavalkar et al. 2018
+    with the CTC likelihood as the hypothesis posterior.  Arguments as nbest_log_likelihood, plus risk (B, N): any
+    numbers (fp32 is used), word errors being the use.  With the live hypotheses those with a finite ll:
+      post = softmax of ll over the live n, rbar = mean of risk over the live n,
+      loss[b] = sum_n post[b, n] * (risk[b, n] - rbar[b])      (0 with fewer than two live hypotheses)
+    Returns the named tuple (loss (B,), ll (B, N), post (B, N)); the gradient flows to logits only:
+      d loss[b] / d logits[b, t, v] = sum_n c[b, n] * occ_n[t, v],  c = post * ((risk - rbar) - loss),
+    occ_n[t, v] the posterior probability that hypothesis n's alignment emits v at frame t.  The softmax term of the
+    CTC gradient cancels (sum_n c = 0) and is never formed: the gradient is exactly zero outside the blank and the
+    hypotheses' labels, beyond each utterance's length, and where the risks are all equal."""
+    blank = int(blank)
+    x, il, h2, ldh, hl, N, ml = _nbest_problem(logits, hyps, hyp_lengths, input_lengths, blank, batch_first, max_labels,
+                                               "expected_risk_loss")
+    if not torch.is_tensor(risk) or not risk.is_cuda:
+        raise RuntimeError("expected_risk_loss runs on libcfm: a CUDA risk tensor required")
+    if risk.numel() != hl.numel():
+        raise ValueError(f"risk must be (B, N) = {(hl.numel() // N, N)}, got {tuple(risk.shape)}")
+    r = risk.detach().to(torch.float32).reshape(-1).contiguous()
+    return ExpectedRisk(*_ExpectedRiskFn.apply(x, il, h2, ldh, hl, N, ml, blank, r, bool(batch_first)))
+
+
+def mwer_loss(logits, targets, input_lengths, target_lengths, nbest=4, beam_size=None, blank=0, pad=-1,
+              batch_first=True, max_labels=None, lm=None, **lm_kw):
+    """Minimum word error rate loss: the expected number of word errors over the beam's own n-best list.  Without
+    gradient, on the detached logits: beam_search_decode(nbest=nbest, beam_size=beam_size or nbest, lm=lm, **lm_kw)
+    and edit_distance of its hypotheses against targets (B, Lr) CUDA ids / target_lengths; hypotheses the beam did not
+    fill (score -inf) are marked missing; then expected_risk_loss on the attached logits with the distances as the
+    risk.  Hypotheses are cut to 511 labels (max_labels None: min(T, 511)); longer ones are not live.
+    Returns (loss (B,), the EditDistance of the n-best list, post (B, N)).  No host synchronisation."""
+    if not isinstance(nbest, int) or isinstance(nbest, bool) or not 1 <= nbest <= NBEST_MAX:
+        raise ValueError(f"nbest must be an integer in [1, {NBEST_MAX}], got {nbest!r}")
+    W = max(int(beam_size) if beam_size else nbest, nbest)
+    with torch.no_grad():
+        tokens, lens, scores = beam_search_decode(logits.detach(), input_lengths, beam_size=W, blank=blank, pad=pad,
+                                                  nbest=nbest, batch_first=batch_first, lm=lm, **lm_kw)
+        width = min(tokens.shape[-1], NBEST_MAX_LABELS)
+        lens = torch.where(scores == float("-inf"), torch.full_like(lens, -1), lens)
+        hyps = tokens[..., :width]
+        ed = edit_distance(hyps, targets, lens, target_lengths)
+        risk = ed.distance.to(torch.float32)
+    out = expected_risk_loss(logits, hyps, lens, risk, input_lengths, blank, batch_first,
+                             width if max_labels is None else max_labels)
+    return out.loss, ed, out.post

@@ -36,6 +36,11 @@ MI355X build (documented in DESIGN.md):
                                            the reference's: it is the corpus WER, 100 * sum(errors) / sum(reference
                                            words) over the epoch or split (0.0 without words), not a mean of batch
                                            figures over padded targets; the loss stays the mean of the per-step values
+  mwer_weight            float | None      None: Runner.train minimises the CTC loss (the reference).  A number
+  mwer_nbest             int               (set_mwer): it minimises ctc + mwer_weight * mean_b(mwer_b), mwer_b the
+                                           expected word errors over the beam's mwer_nbest best hypotheses
+                                           (ctc.mwer_loss; beam width max(beam_size, mwer_nbest)); history["loss"]
+                                           stays the CTC loss, history["mwer"] records the term
 """
 from __future__ import annotations
 
@@ -82,7 +87,7 @@ _NST_LM = dict(nst=True, lm=False, train_lm=False, ft_lr=3e-6, ft_epochs=3, ft_t
 _BUILD = dict(compute_dtype="bf16", frontend_proj="utterance", pos_enc="none", use_group_norm=False,
               specaug_ref_noop_masks=False, dp_world_size=1, layer_norm_eps=1e-5, bn_eps=1e-5, bn_momentum=0.1, beam_size=0,
               decoder_lm=None, lm_weight=0.0, word_bonus=0.0, token_beam=0, nst_min_confidence=None,
-              decoder_batched=False, device_wer=False)
+              decoder_batched=False, device_wer=False, mwer_weight=None, mwer_nbest=4)
 
 
 class HParams:
@@ -162,6 +167,18 @@ class HParams:
         loss: no host synchronisation per step.  Not the reference's figure (the mean over batches of a WER whose
         targets are padded with '_'), which False (the default) keeps."""
         self.device_wer = bool(flag)
+
+    def set_mwer(self, weight, nbest=4):
+        """MWER training (Prabhavalkar et al. 2018): with weight a number, Runner.train minimises
+        ctc + weight * mean_b(mwer_b), mwer_b = ctc.mwer_loss of utterance b: the expected number of word errors over
+        the `nbest` best hypotheses of a beam search (width max(beam_size, nbest), the decoder LM fused if one is set)
+        on the step's own logits, the hypotheses weighted by their CTC likelihood.  The mean runs over the batch_size
+        rows, as the CTC mean does.  history["loss"] stays the CTC loss alone; history["mwer"] records the term.
+        None (the default) switches it off: the training step is then the reference's."""
+        self.mwer_weight = None if weight is None else float(weight)
+        self.mwer_nbest = int(nbest)
+        if not 1 <= self.mwer_nbest <= 128:
+            raise ValueError(f"mwer nbest must be in [1, 128], got {nbest}")
 
     def set_ntokens(self, ntokens):
         self.ntokens = ntokens

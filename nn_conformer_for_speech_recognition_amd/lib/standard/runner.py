@@ -28,6 +28,10 @@ Same constructor, methods and control flow as the reference; what runs underneat
   confusion    Runner.test(heatmap=True): the aligned pairs of ctc.edit_distance(ops=True) as a (V + 1, V + 1) count
                matrix (row: reference word, column: hypothesis word, index V: the gap) on self.confusion[split] and
                in hp.plots_dir/confusion_<split>.json (evals.py:64 builds it with sklearn and plots it).
+  MWER         hp.mwer_weight (default None: the CTC loss alone, the step unchanged; HParams.set_mwer): train minimises
+               ctc + weight * mean_b(mwer_b), mwer_b = ctc.mwer_loss: the expected word errors over the beam's
+               hp.mwer_nbest best hypotheses of the step's own logits (no reference counterpart).  history["loss"] stays
+               the CTC loss; history["mwer"] holds the epoch's mean of the term, accumulated on the device.
 
 Dropped (outside the hot path): tqdm colours, Evals plots (losses / WER are kept on
 the Runner as .history and written to hp.plots_dir/history.json), the transformer-LM weight fusion (fuse_models).
@@ -43,7 +47,7 @@ from statistics import mean
 import torch
 import torch.nn as nn
 
-from ...ctc import CTCLoss, beam_search_decode, edit_distance, forced_align, greedy_decode
+from ...ctc import CTCLoss, beam_search_decode, edit_distance, forced_align, greedy_decode, mwer_loss
 from ...optim import Adafactor
 from .myvocab import wer
 
@@ -102,9 +106,9 @@ class Runner:
                                   "path; for n-gram shallow fusion in the decoder see HParams.set_decoder_lm")
 
     # ----------------------------------------------------------------------------- train / test
-    def _beam_search(self, voc, logits, lengths):
-        """The hp.beam_size search of the metric and label passes -> (fp32 logits, lengths padded / truncated to the
-        batch, tokens (B, 1, T) int32, counts (B, 1))."""
+    def _beam_settings(self, logits, lengths):
+        """What every beam search of the Runner shares -> (fp32 logits, lengths padded / truncated to the batch, the
+        decoder LM's keyword arguments)."""
         if lengths is not None:
             B = logits.shape[0]
             lengths = nn.functional.pad(lengths[:B], (0, max(0, B - lengths.shape[0])))
@@ -114,9 +118,28 @@ class Runner:
             kw = dict(lm=lm, lm_weight=float(self.hp.lm_weight), word_bonus=float(self.hp.word_bonus),
                       token_beam=int(self.hp.token_beam) or None)
         logits = logits.float() if logits.dtype != torch.float32 else logits
+        return logits, lengths, kw
+
+    def _beam_search(self, voc, logits, lengths):
+        """The hp.beam_size search of the metric and label passes -> (fp32 logits, lengths padded / truncated to the
+        batch, tokens (B, 1, T) int32, counts (B, 1))."""
+        logits, lengths, kw = self._beam_settings(logits, lengths)
         toks, cnt, _ = beam_search_decode(logits, lengths, beam_size=int(self.hp.beam_size), blank=voc.blank_idx,
                                           pad=voc.pad_idx, **kw)
         return logits, lengths, toks, cnt
+
+    def _mwer(self, voc, logits, target, target_lens, lengths):
+        """hp.mwer_weight set: mean over the hp.batch_size rows of ctc.mwer_loss on the step's logits (attached), the
+        search through _beam_settings with width max(hp.beam_size, hp.mwer_nbest).  Rows without a target row (and
+        padded rows: no frames, one empty hypothesis) contribute 0.  Nothing is read back."""
+        nbest = int(self.hp.mwer_nbest)
+        logits, lengths, kw = self._beam_settings(logits, lengths)
+        n = min(logits.shape[0], target.shape[0])
+        T = logits.shape[1]
+        loss, _, _ = mwer_loss(logits[:n], target[:n], None if lengths is None else lengths[:n], target_lens[:n],
+                               nbest=nbest, beam_size=max(int(getattr(self.hp, "beam_size", 0)), nbest),
+                               blank=voc.blank_idx, pad=voc.pad_idx, max_labels=min(T, 511), **kw)
+        return loss.sum() / self.hp.batch_size
 
     def _beam_labels(self, voc, logits, lengths, confidence=False):
         """hp.beam_size > 0: the best prefix-beam-search hypothesis per utterance as label strings (lengths: the
@@ -215,11 +238,14 @@ class Runner:
         train_size = ceil(len(train_set.idxes[dataset_type]) / self.hp.batch_size)
         want_wer = getattr(self.hp, "train_wer", True)     # WER forces a host sync per step
         device_wer = bool(getattr(self.hp, "device_wer", False))
+        mwer_weight = getattr(self.hp, "mwer_weight", None)     # None: the CTC loss alone (HParams.set_mwer)
         for _ in range(epochs):
             self.model.train()
             train_set.shuffle(dataset_type)
             eloss, emetric = [], []
             acc = self._new_accumulator() if device_wer else None
+            if mwer_weight is not None:     # the epoch's sum of the MWER term, on the device, read once
+                mwer_sum = torch.zeros((), dtype=torch.float64, device=self.hp.device)
             for i in range(train_size):
                 batch = train_set.get_batch(i, dataset_type)
                 inbatch, input_lens = batch["input"]["mels"], batch["input"]["tau"]
@@ -229,8 +255,13 @@ class Runner:
                 output_lengths = nn.functional.pad(output_lengths, (0, self.hp.batch_size - output_lengths.shape[0]))
                 output_lengths = output_lengths.clamp(max=logits.shape[1])
                 loss = self.loss(logits.transpose(0, 1), target, output_lengths, target_lens)
+                objective = loss
+                if mwer_weight is not None:     # ctc + weight * mean_b(mwer_b); `loss` stays the CTC loss alone
+                    mwer = self._mwer(train_set.vocab, logits, target, target_lens, output_lengths)
+                    objective = loss + mwer_weight * mwer
+                    mwer_sum += mwer.detach().double()
                 if device_wer:     # loss and word errors stay on the device: no host sync in the step
-                    loss.backward()
+                    objective.backward()
                     self.optimizer.step()
                     with torch.no_grad():
                         ed = self._edit_distance(train_set, logits.detach(), target, target_lens,
@@ -238,7 +269,7 @@ class Runner:
                         self._accumulate(acc, ed, loss)
                     continue
                 cur = loss.item()
-                loss.backward()
+                objective.backward()
                 self.optimizer.step()
                 eloss.append(cur)
                 if want_wer:
@@ -251,6 +282,8 @@ class Runner:
             else:
                 self.history["loss"].append(mean([100 if isnan(x) else x for x in eloss]))
                 self.history["metric"].append(mean(emetric) if emetric else float("nan"))
+            if mwer_weight is not None:
+                self.history.setdefault("mwer", []).append(mwer_sum.item() / train_size if train_size else float("nan"))
             if "validation" in train_set.idxes:
                 vl, vm = self.test(train_set, "validation", finetuning=finetuning)
                 self.history["val_loss"].append(vl)

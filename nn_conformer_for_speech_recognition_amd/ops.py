@@ -1151,6 +1151,35 @@ def ctc_forced_align(x, targets_i32, ldt, tgt_off, in_len_i32, tgt_len_i32, smax
     return alignments, scores, score, starts, ends, token_scores
 
 
+def ctc_nbest_fwd(x, in_len_i32, hyp_i32, ldh, hyp_len_i32, N, max_labels, blank, risk=None, batch_first=True):
+    """CTC likelihoods of an n-best list and the expected risk over it (cfm_ctc_nbest_fwd): hypothesis j = b * N + n
+    is row hyp_i32 + j * ldh with hyp_len_i32[j] labels (< 0: missing).  -> (ll (B, N), post (B, N), loss (B,) or None
+    without risk, ws for ctc_nbest_bwd), fp32."""
+    B, T, sb, st = _rows(x, batch_first)
+    dev = x.device
+    ll = torch.empty(B, N, device=dev, dtype=torch.float32)
+    post = torch.empty(B, N, device=dev, dtype=torch.float32)
+    loss = None if risk is None else torch.empty(B, device=dev, dtype=torch.float32)
+    ws = workspace(L.size_call("cfm_ctc_nbest_ws_bytes", B, T, int(N), int(max_labels)), dev)
+    L.call("cfm_ctc_nbest_fwd", L.ptr(x), sb, st, L.ptr(in_len_i32), B, T, x.shape[-1], L.ptr(hyp_i32) or None,
+           int(ldh), L.ptr(hyp_len_i32), int(N), int(max_labels), int(blank), L.ptr(risk), L.ptr(ll), L.ptr(post),
+           L.ptr(loss), L.ptr(ws), L.stream())
+    return ll, post, loss, ws
+
+
+def ctc_nbest_bwd(x, in_len_i32, hyp_i32, ldh, hyp_len_i32, N, max_labels, blank, ws, grad_loss, batch_first=True):
+    """d (sum_b grad_loss[b] * loss[b]) / d logits of ctc_nbest_fwd (cfm_ctc_nbest_bwd), fp32, in x's layout: zero
+    outside the blank and the hypotheses' labels, no softmax term."""
+    B, T, sb, st = _rows(x, batch_first)
+    g = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    _, _, gsb, gst = _rows(g, batch_first)
+    go = grad_loss.float().contiguous()
+    L.call("cfm_ctc_nbest_bwd", L.ptr(x), sb, st, L.ptr(in_len_i32), B, T, x.shape[-1], L.ptr(hyp_i32) or None,
+           int(ldh), L.ptr(hyp_len_i32), int(N), int(max_labels), int(blank), L.ptr(ws), L.ptr(go),
+           1 if go.numel() > 1 else 0, L.ptr(g), gsb, gst, L.stream())
+    return g
+
+
 def edit_distance(ref_i32, ldr, ref_len_i32, hyp_i32, ldh, hyp_len_i32, P, group, rmax, hmax, want_ops=False,
                   out=None):
     """Batched edit distance over token ids (cfm_edit_distance): pair p compares hypothesis row p (hyp_i32 + p * ldh)
