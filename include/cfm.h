@@ -758,41 +758,40 @@ int cfm_ffold_bwd_weights(const float* H, const float* S, const float* w1, const
                           const cfm_ffold_geo* g, void* stream);
 
 /* ---------------------------------------------------------------- Adafactor (runner.py:36)
- * transformers.Adafactor(lr, beta1, scale_parameter=False, relative_step=False) as one
- * multi-tensor step.  The host fills a parameter table (cfm_adafactor_fill_table into a host
- * buffer of cfm_adafactor_table_bytes(n)), copies it to the device, and calls
- * cfm_adafactor_step with the prefix totals (factored rows, factored columns, elementwise
- * blocks = sum of cfm_adafactor_blocks(numel)).  col == NULL marks an unfactored (1-D) tensor,
- * whose full second moment lives in `row`.  rowmean: >= sum(nb) floats. */
+ * transformers.Adafactor as one multi-tensor step over a device-side parameter table.  A parameter
+ * is nb matrices of R x C (col == NULL, factored == 0: a 1-D tensor, its full second moment in
+ * `row`).  cfm_adafactor_plan is the one rule of what each parameter adds to each launch (host
+ * arithmetic on the geometry, never the pointers).  cfm_adafactor_fill_table writes all n entries
+ * of a host buffer of cfm_adafactor_table_bytes(n) through it; the totals size the buffers and go
+ * to cfm_adafactor_step with the device copy of the table. */
+typedef struct { float* p; const float* g; float* m; float* row; float* col;
+                 long numel; int nb, R, C, factored; } cfm_adafactor_param;
+typedef struct {
+  long row_tasks, cols, blocks;         /* ada_rows waves, ada_cols threads, blocks of 4096 elements */
+  long rowmean_tasks, colpart_tasks;    /* ada_rowmean waves, ada_colpart blocks (C in 64..2560) */
+  long rowmean_floats, part_floats;     /* floats of rowmean and of part (may be NULL when 0) */
+} cfm_adafactor_totals;
+/* partial: blocks floats, per-block u^2 sums (RMS summed in block order, deterministic);
+ * partial_p: the same of p^2, and rms_out: n floats, both SCALE_PARAMETER only. */
+typedef struct { float *rowmean, *part, *partial, *partial_p, *rms_out; } cfm_adafactor_buffers;
 size_t cfm_adafactor_table_bytes(int n_params);
-int cfm_adafactor_fill_table(void* host_table, int i, float* p, const float* g, float* m, float* row,
-                             float* col, long numel, int nb, int R, int C, long row_task_off,
-                             long col_off, long blk_off, long rm_off, long rm_task_off,
-                             long colpart_task_off, long part_off);
-int cfm_adafactor_blocks(long numel);
-long cfm_adafactor_row_tasks(int nb, int R, int C);
-long cfm_adafactor_rowmean_tasks(int nb, int R);
-long cfm_adafactor_colpart_tasks(int nb, int R, int C);
-long cfm_adafactor_part_floats(int nb, int R, int C);
-/* part: >= sum of cfm_adafactor_part_floats floats (column partials of wide matrices);
-   partial: >= nblocks floats (per-block u^2 sums; RMS summed in block order, deterministic). */
-int cfm_adafactor_step(const void* dev_table, int n, long nrow_tasks, long ncols, long nblocks,
-                       long nrowmean_tasks, long ncolpart_tasks, float* rowmean, float* part,
-                       float* partial, float lr, float beta1, float beta2t, float eps1, float clip,
-                       void* stream);
-/* The rest of transformers.Adafactor on the same table, tasks and buffers: scale_parameter,
- * weight_decay, and a step whose scalars live on the device (graph-capturable).  Per tensor
+/* before (may be NULL): n entries, the totals in front of each parameter = its offsets in the table */
+int cfm_adafactor_plan(const cfm_adafactor_param* params, int n, cfm_adafactor_totals* before,
+                       cfm_adafactor_totals* totals);
+int cfm_adafactor_fill_table(void* host_table, const cfm_adafactor_param* params, int n,
+                             cfm_adafactor_totals* totals);
+/* The step; the kernel variants it launches are a function of the hyper-parameters alone.  Per tensor
  *   lr_p = rel * (SCALE_PARAMETER ? max(eps2, RMS(p)) : 1),   RMS(p) = ||p|| / sqrt(numel) of p
  *          before this step (written to rms_out[i], i = table index; per-block sums of p^2 in
- *          partial_p, >= nblocks floats, summed in block order as `partial` is),
+ *          partial_p, summed in block order as `partial` is),
  *   p += -weight_decay * lr_p * p  before  p -= update.
- * Without DEVICE_STEP rel = lr and beta2t is the argument, as in cfm_adafactor_step (the host has
- * resolved a relative step already; RELATIVE_STEP / WARMUP_INIT are not read).  With DEVICE_STEP
+ * Without DEVICE_STEP rel = lr and beta2t is the field (the host has resolved a relative step
+ * already; RELATIVE_STEP / WARMUP_INIT are not read).  With DEVICE_STEP
  * one extra launch increments *step_dev (int32) and writes scalars_dev[0] = beta2t =
  * 1 - step^decay_rate and scalars_dev[1] = rel = RELATIVE_STEP ? min(WARMUP_INIT ? 1e-6 step :
  * 1e-2, 1/sqrt(step)) : lr (both computed in double, rounded once), which the other kernels read:
  * no host value depends on the step, so one captured launch sequence replays as successive steps.
- * flags == 0 and weight_decay == 0 launches exactly what cfm_adafactor_step launches. */
+ * flags == 0 and weight_decay == 0 launch the six kernels of the reference's configuration. */
 enum cfm_adafactor_flags {
   CFM_ADA_SCALE_PARAMETER = 1 << 0,
   CFM_ADA_RELATIVE_STEP = 1 << 1,
@@ -806,10 +805,8 @@ typedef struct {
   int* step_dev;       /* DEVICE_STEP: one int32, incremented by the call */
   float* scalars_dev;  /* DEVICE_STEP: 2 floats */
 } cfm_adafactor_hyper;
-int cfm_adafactor_step_ex(const void* dev_table, int n, long nrow_tasks, long ncols, long nblocks,
-                          long nrowmean_tasks, long ncolpart_tasks, float* rowmean, float* part,
-                          float* partial, float* partial_p, float* rms_out,
-                          const cfm_adafactor_hyper* hyper, void* stream);
+int cfm_adafactor_step(const void* dev_table, int n, const cfm_adafactor_totals* totals,
+                       const cfm_adafactor_buffers* buffers, const cfm_adafactor_hyper* hyper, void* stream);
 
 /* ---------------------------------------------------------------- CTC head (runner.py:35,142-143)
  * Replaces torch.nn.CTCLoss(blank=hp.blank_idx, zero_infinity=True) on

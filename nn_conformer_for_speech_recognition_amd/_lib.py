@@ -157,8 +157,25 @@ class FfoldGeo(ctypes.Structure):
         ("xt_elems", c_long), ("ws_floats", c_long)]
 
 
+class AdafactorParam(ctypes.Structure):
+    """cfm_adafactor_param (include/cfm.h): one parameter as cfm_adafactor_plan / _fill_table read it."""
+    _fields_ = [(n, c_void_p) for n in ("p", "g", "m", "row", "col")] + [("numel", c_long)] + [
+        (n, c_int) for n in ("nb", "R", "C", "factored")]
+
+
+class AdafactorTotals(ctypes.Structure):
+    """cfm_adafactor_totals (include/cfm.h): the plan's sums over a group, or those in front of one parameter."""
+    _fields_ = [(n, c_long) for n in ("row_tasks", "cols", "blocks", "rowmean_tasks", "colpart_tasks",
+                                      "rowmean_floats", "part_floats")]
+
+
+class AdafactorBuffers(ctypes.Structure):
+    """cfm_adafactor_buffers (include/cfm.h)."""
+    _fields_ = [(n, c_void_p) for n in ("rowmean", "part", "partial", "partial_p", "rms_out")]
+
+
 class AdafactorHyper(ctypes.Structure):
-    """cfm_adafactor_hyper (include/cfm.h): what cfm_adafactor_step_ex takes beyond the table and the buffers."""
+    """cfm_adafactor_hyper (include/cfm.h): the scalars and variant flags of one cfm_adafactor_step."""
     _fields_ = [("decay_rate", ctypes.c_double)] + [(n, c_float) for n in (
         "lr", "beta1", "beta2t", "eps1", "eps2", "clip", "weight_decay")] + [
         ("flags", c_int), ("step_dev", c_void_p), ("scalars_dev", c_void_p)]
@@ -253,19 +270,9 @@ _SIGS = {
     "cfm_bn_silu_bwd_apply": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_long, c_void_p, c_long, c_int, c_void_p]),
     "cfm_adafactor_table_bytes": (c_size_t, [c_int]),
-    "cfm_adafactor_fill_table": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long,
-                                         c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_long, c_long,
-                                         c_long]),
-    "cfm_adafactor_colpart_tasks": (c_long, [c_int, c_int, c_int]),
-    "cfm_adafactor_part_floats": (c_long, [c_int, c_int, c_int]),
-    "cfm_adafactor_blocks": (c_int, [c_long]),
-    "cfm_adafactor_row_tasks": (c_long, [c_int, c_int, c_int]),
-    "cfm_adafactor_rowmean_tasks": (c_long, [c_int, c_int]),
-    "cfm_adafactor_step": (c_int, [c_void_p, c_int, c_long, c_long, c_long, c_long, c_long, c_void_p, c_void_p,
-                                   c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p]),
-    # (..., rowmean, part, partial, partial_p, rms_out, const cfm_adafactor_hyper*, stream)
-    "cfm_adafactor_step_ex": (c_int, [c_void_p, c_int, c_long, c_long, c_long, c_long, c_long, c_void_p, c_void_p,
-                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cfm_adafactor_plan": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),    # (params, n, before or NULL, totals)
+    "cfm_adafactor_fill_table": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "cfm_adafactor_step": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cfm_silu_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_long, c_void_p]),
     "cfm_bn_ws_bytes": (c_size_t, [c_int]),
     "cfm_bn_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_void_p,

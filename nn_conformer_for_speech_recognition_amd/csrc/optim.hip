@@ -13,19 +13,18 @@
 // adapts to the tensor: a wide row (C >= 64) is one wave, narrow rows (e.g. the 3x3 taps of the
 // conv2 weight, nb = 65536) are packed 64 per wave (one per lane).  HBM-bound.
 //
-// cfm_adafactor_step_ex adds the rest of transformers.Adafactor to the same launches: scale_parameter (the step
+// The hyper-parameters add the rest of transformers.Adafactor to the same launches: scale_parameter (the step
 // size times max(eps2, RMS(p)); the u^2 pass also sums p^2 per block), weight_decay, and a device-side step
 // (ada_scalars: step count, beta2t and relative step size in device memory, so a captured launch sequence
-// replays as successive steps).  All of it is compile-time variants: the kernels cfm_adafactor_step launches
+// replays as successive steps).  All of it is compile-time variants: the kernels a step without them launches
 // (<float>, <false>) have the instruction stream they had before the variants existed.
-#include "cfm_common.h"
+#include <vector>
+
+#include "ada_plan.h"
 
 namespace {
 
 constexpr int EB = 256;          // threads per block
-constexpr int CHUNK = 4096;      // elements per block in the elementwise passes
-constexpr int RB = 32;           // rows per column-partial task (wide factored tensors)
-constexpr int KMAX = 40;         // 64-column groups a lane keeps in registers: wide means 64 <= C <= 2560
 
 // unsigned 32-bit division by an invariant divisor d >= 1 (Granlund-Montgomery): with l = ceil(log2 d) and
 // m = floor(2^32 (2^l - d) / d) + 1, n / d = (t + ((n - t) >> 1)) >> (l - 1) for t = mulhi(m, n) (d >= 2);
@@ -44,21 +43,18 @@ __device__ __forceinline__ uint32_t udiv(uint32_t n, const UDiv& v) {
   return (t + ((n - t) >> 1)) >> v.sh;
 }
 
-struct AdaP {
-  float* p; const float* g; float* m; float* row; float* col;   // col == nullptr: unfactored (row = v)
-  long numel; int nb, R, C, factored;
-  long row_toff, col_off, blk_off, rm_off, rm_toff;              // prefix offsets (tasks / elements)
-  long cp_toff, part_off;                                        // column-partial tasks / partial floats
-  UDiv div_rc, div_c;                                            // element index -> (matrix, row, column)
+// a table entry: the parameter (col == nullptr: unfactored, row = v), the plan's totals in front of it (tasks /
+// elements / workspace floats), and its element index -> (matrix, row, column) divisions
+struct AdaP : cfm_adafactor_param {
+  long row_toff, col_off, blk_off, rm_off, rm_toff, cp_toff, part_off;
+  UDiv div_rc, div_c;
 };
 
-__host__ __device__ __forceinline__ bool is_wide(int C) { return C >= 64 && C <= 64 * KMAX; }
-
-__device__ __forceinline__ long off_of(const AdaP& q, int which) {
-  return which == 0 ? q.row_toff : which == 1 ? q.col_off : which == 2 ? q.blk_off : which == 3 ? q.rm_toff
-                                                                                                  : q.cp_toff;
+__device__ __forceinline__ long off_of(const AdaP& q, AdaPhase which) {
+  return which == ADA_ROWS ? q.row_toff : which == ADA_COLS ? q.col_off : which == ADA_BLOCKS ? q.blk_off
+         : which == ADA_ROWMEAN ? q.rm_toff : q.cp_toff;
 }
-__device__ __forceinline__ int find_param(const AdaP* t, int n, long idx, int which) {
+__device__ __forceinline__ int find_param(const AdaP* t, int n, long idx, AdaPhase which) {
   int lo = 0, hi = n - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -67,7 +63,7 @@ __device__ __forceinline__ int find_param(const AdaP* t, int n, long idx, int wh
   return lo;
 }
 
-// beta2t reaches a kernel as the host's float (B2 = float: the kernels cfm_adafactor_step launches), or is read
+// beta2t reaches a kernel as the host's float (B2 = float: the kernels a host-scalar step launches), or is read
 // from the device step scalars that ada_scalars writes (B2 = const float*: the capturable step)
 constexpr int SC_B2T = 0, SC_REL = 1;   // scalar block: beta2t, relative step size
 __device__ __forceinline__ float b2t_of(float v) { return v; }
@@ -87,7 +83,7 @@ __global__ __launch_bounds__(EB) void ada_colpart(const AdaP* __restrict__ t, in
   __shared__ float red[4][64 * KMAX];
   const long task = blockIdx.x;
   if (task >= ntasks) return;
-  const AdaP& q = t[find_param(t, n, task, 4)];
+  const AdaP& q = t[find_param(t, n, task, ADA_COLPART)];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int nrb = (q.R + RB - 1) / RB;
   const long lt = task - q.cp_toff;
@@ -171,10 +167,9 @@ __global__ __launch_bounds__(EB) void ada_colpart(const AdaP* __restrict__ t, in
   for (int c = threadIdx.x; c < q.C; c += EB) dst[c] = red[0][c] + red[1][c] + red[2][c] + red[3][c];
 }
 
-// row tasks of NARROW factored tensors: 256 rows per wave (lane = 4 rows; a task per 64 rows left each wave's
-// parameter search -- ~9 dependent table loads -- in front of one 4-byte row: ~18.6 M such rows at L15, the
-// degenerate (O, I, 1) pointwise-conv weights, ran 95 us)
-constexpr int ROWS_PER_TASK = 256;
+// row tasks of NARROW factored tensors: ROWS_PER_TASK = 256 rows per wave (lane = 4 rows; a task per 64 rows left
+// each wave's parameter search -- ~9 dependent table loads -- in front of one 4-byte row: ~18.6 M such rows at L15,
+// the degenerate (O, I, 1) pointwise-conv weights, ran 95 us)
 template <class B2>
 __global__ void ada_rows(const AdaP* __restrict__ t, int n, long ntasks, B2 b2, float eps1) {
   const float b2t = b2t_of(b2);
@@ -182,7 +177,7 @@ __global__ void ada_rows(const AdaP* __restrict__ t, int n, long ntasks, B2 b2, 
   // wave-uniform task made provably uniform: the parameter search and the table fields become scalar loads
   const long task = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (task >= ntasks) return;
-  const AdaP& q = t[find_param(t, n, task, 0)];
+  const AdaP& q = t[find_param(t, n, task, ADA_ROWS)];
   const long lt = task - q.row_toff;
   if (is_wide(q.C)) {      // (wide rows are done by ada_colpart; kept for a wide tensor with no tasks)
     const float* g = q.g + lt * q.C;
@@ -227,7 +222,7 @@ __global__ void ada_cols(const AdaP* __restrict__ t, int n, long ncols, B2 b2, f
   const long cidx = (long)blockIdx.x * EB + threadIdx.x;
   if (cidx >= ncols) return;
   // the block's first column's parameter by a uniform (scalar) search, then a short per-lane forward scan
-  int pi = find_param(t, n, (long)blockIdx.x * EB, 1);
+  int pi = find_param(t, n, (long)blockIdx.x * EB, ADA_COLS);
   while (pi + 1 < n && t[pi + 1].col_off <= cidx) ++pi;
   const AdaP& q = t[pi];
   const long lc = cidx - q.col_off;     // = b*C + j
@@ -266,7 +261,7 @@ __global__ void ada_rowmean(const AdaP* __restrict__ t, int n, long ntasks, floa
   const int lane = threadIdx.x & 63;
   const long task = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (task >= ntasks) return;
-  const AdaP& q = t[find_param(t, n, task, 3)];
+  const AdaP& q = t[find_param(t, n, task, ADA_ROWMEAN)];
   if (!q.factored) return;
   const long lt = task - q.rm_toff;
   if (q.R >= 64) {
@@ -328,7 +323,7 @@ __device__ __forceinline__ bool vec4_ok(const AdaP& q) {
 }
 
 // What scale_parameter / weight_decay / the device step add to the two elementwise kernels, as a trailing kernel
-// argument that is empty without them (<false>: the kernels cfm_adafactor_step launches; no extra load or store).
+// argument that is empty without them (<false>: the kernels of a step without them; no extra load or store).
 template <bool PRMS> struct SumsqEx {};
 template <> struct SumsqEx<true> { float* partial_p; };   // per-block sums of p^2
 template <bool EX> struct ApplyEx {};
@@ -348,7 +343,7 @@ __global__ __launch_bounds__(EB) void ada_sumsq(const AdaP* __restrict__ t, int 
   const float b2t = b2t_of(b2);
   __shared__ float red[EB / 64];
   __shared__ float redp[PRMS ? EB / 64 : 1];
-  const int pi = find_param(t, n, blockIdx.x, 2);
+  const int pi = find_param(t, n, blockIdx.x, ADA_BLOCKS);
   const AdaP& q = t[pi];
   const long start = (long)(blockIdx.x - q.blk_off) * CHUNK;
   const long end = min(q.numel, start + CHUNK);
@@ -395,7 +390,7 @@ __global__ __launch_bounds__(EB) void ada_apply(const AdaP* __restrict__ t, int 
                                                 float beta1, float clip, ApplyEx<EX> ex) {
   __shared__ float red[EB / 64];
   __shared__ float redp[EX ? EB / 64 : 1];
-  const int pi = find_param(t, n, blockIdx.x, 2);
+  const int pi = find_param(t, n, blockIdx.x, ADA_BLOCKS);
   const AdaP& q = t[pi];
   // RMS(u) of the whole tensor: its blocks' partials in block order
   const int nblk = (int)((q.numel + CHUNK - 1) / CHUNK);
@@ -497,104 +492,71 @@ __global__ void ada_scalars(int* __restrict__ step, float* __restrict__ sc, doub
 
 CFM_EXPORT size_t cfm_adafactor_table_bytes(int n_params) { return (size_t)n_params * sizeof(AdaP); }
 
-CFM_EXPORT int cfm_adafactor_fill_table(void* host_table, int i, float* p, const float* g, float* m, float* row,
-                                        float* col, long numel, int nb, int R, int C, long row_toff, long col_off,
-                                        long blk_off, long rm_off, long rm_toff, long cp_toff, long part_off) {
-  CFM_REQUIRE(host_table && p && g && row, CFM_ERR_ARG, "null pointer");
-  CFM_REQUIRE(numel < (1L << 31), CFM_ERR_SHAPE, "tensor too large (2^31 elements)");
-  AdaP* t = reinterpret_cast<AdaP*>(host_table) + i;
-  t->p = p; t->g = g; t->m = m; t->row = row; t->col = col;
-  t->numel = numel; t->nb = nb; t->R = R; t->C = C; t->factored = col != nullptr;
-  t->div_rc = udiv_make((uint32_t)R * (uint32_t)C);
-  t->div_c = udiv_make((uint32_t)C);
-  t->row_toff = row_toff; t->col_off = col_off; t->blk_off = blk_off; t->rm_off = rm_off; t->rm_toff = rm_toff;
-  t->cp_toff = cp_toff; t->part_off = part_off;
+CFM_EXPORT int cfm_adafactor_fill_table(void* host_table, const cfm_adafactor_param* params, int n,
+                                        cfm_adafactor_totals* totals) {
+  CFM_REQUIRE(host_table, CFM_ERR_ARG, "bad args");
+  std::vector<cfm_adafactor_totals> before(n > 0 ? n : 0);
+  if (const int rc = cfm_adafactor_plan(params, n, before.data(), totals)) return rc;
+  static_assert(sizeof(AdaP) == 144, "no padding: the host compares tables byte by byte");
+  for (int i = 0; i < n; ++i) {
+    const cfm_adafactor_param& q = params[i];
+    const cfm_adafactor_totals& b = before[i];
+    CFM_REQUIRE(q.p && q.g && q.row && (q.col != nullptr) == (q.factored != 0), CFM_ERR_ARG, "null pointer");
+    reinterpret_cast<AdaP*>(host_table)[i] =
+        AdaP{q, b.row_tasks, b.cols, b.blocks, b.rowmean_floats, b.rowmean_tasks, b.colpart_tasks, b.part_floats,
+             udiv_make((uint32_t)q.R * (uint32_t)q.C), udiv_make((uint32_t)q.C)};
+  }
   return CFM_OK;
 }
 
-CFM_EXPORT int cfm_adafactor_blocks(long numel) { return (int)((numel + CHUNK - 1) / CHUNK); }
-
-// number of row tasks / row-mean tasks / column-partial tasks / partial floats a factored tensor
-// contributes (see ada_rows / ada_rowmean / ada_colpart)
-CFM_EXPORT long cfm_adafactor_row_tasks(int nb, int R, int C) {
-  return is_wide(C) ? 0 : ((long)nb * R + ROWS_PER_TASK - 1) / ROWS_PER_TASK;
-}
-CFM_EXPORT long cfm_adafactor_colpart_tasks(int nb, int R, int C) { return is_wide(C) ? (long)nb * ((R + RB - 1) / RB) : 0; }
-CFM_EXPORT long cfm_adafactor_part_floats(int nb, int R, int C) {
-  return is_wide(C) ? (long)nb * ((R + RB - 1) / RB) * C : 0;
-}
-CFM_EXPORT long cfm_adafactor_rowmean_tasks(int nb, int R) { return R >= 64 ? (long)nb : ((long)nb + 63) / 64; }
-
-CFM_EXPORT int cfm_adafactor_step(const void* dev_table, int n, long nrow_tasks, long ncols, long nblocks,
-                                  long nrm_tasks, long ncp_tasks, float* rowmean, float* part, float* partial,
-                                  float lr, float beta1, float beta2t, float eps1, float clip, void* stream) {
-  CFM_REQUIRE(dev_table && rowmean && partial && n > 0 && (ncp_tasks == 0 || part), CFM_ERR_ARG, "bad args");
-  const AdaP* t = reinterpret_cast<const AdaP*>(dev_table);
-  hipStream_t s = cfm::as_stream(stream);
-  if (ncp_tasks > 0)
-    hipLaunchKernelGGL(ada_colpart<float>, dim3((unsigned)ncp_tasks), dim3(EB), 0, s, t, n, ncp_tasks, beta2t, eps1,
-                       part);
-  if (nrow_tasks > 0)
-    hipLaunchKernelGGL(ada_rows<float>, dim3((unsigned)((nrow_tasks + 3) / 4)), dim3(256), 0, s, t, n, nrow_tasks,
-                       beta2t, eps1);
-  if (ncols > 0)
-    hipLaunchKernelGGL(ada_cols<float>, dim3((unsigned)((ncols + EB - 1) / EB)), dim3(EB), 0, s, t, n, ncols, beta2t,
-                       eps1, part);
-  if (nrm_tasks > 0)
-    hipLaunchKernelGGL(ada_rowmean, dim3((unsigned)((nrm_tasks + 3) / 4)), dim3(256), 0, s, t, n, nrm_tasks, rowmean);
-  hipLaunchKernelGGL((ada_sumsq<false, float>), dim3((unsigned)nblocks), dim3(EB), 0, s, t, n, rowmean, beta2t, eps1,
-                     partial, SumsqEx<false>{});
-  hipLaunchKernelGGL(ada_apply<false>, dim3((unsigned)nblocks), dim3(EB), 0, s, t, n, rowmean, beta2t, eps1, partial,
-                     lr, beta1, clip, ApplyEx<false>{});
-  return cfm::check_launch("cfm_adafactor_step");
-}
-
-CFM_EXPORT int cfm_adafactor_step_ex(const void* dev_table, int n, long nrow_tasks, long ncols, long nblocks,
-                                     long nrm_tasks, long ncp_tasks, float* rowmean, float* part, float* partial,
-                                     float* partial_p, float* rms_out, const cfm_adafactor_hyper* h, void* stream) {
+// The launch sequence of one step: the grids from the plan's totals, the variant from the hyper-parameters alone.
+CFM_EXPORT int cfm_adafactor_step(const void* dev_table, int n, const cfm_adafactor_totals* tot,
+                                  const cfm_adafactor_buffers* buf, const cfm_adafactor_hyper* h, void* stream) {
   CFM_REQUIRE(h, CFM_ERR_ARG, "null hyper-parameters");
   const bool dev = h->flags & CFM_ADA_DEVICE_STEP, scale = h->flags & CFM_ADA_SCALE_PARAMETER;
   CFM_REQUIRE(!dev || (h->step_dev && h->scalars_dev), CFM_ERR_ARG, "device step without step / scalar pointers");
-  CFM_REQUIRE(!scale || (partial_p && rms_out), CFM_ERR_ARG, "scale_parameter without the p^2 partial / RMS buffers");
-  if (!dev && !scale && h->weight_decay == 0.f)   // nothing to add: the very same launches
-    return cfm_adafactor_step(dev_table, n, nrow_tasks, ncols, nblocks, nrm_tasks, ncp_tasks, rowmean, part, partial,
-                              h->lr, h->beta1, h->beta2t, h->eps1, h->clip, stream);
-  CFM_REQUIRE(dev_table && rowmean && partial && n > 0 && (ncp_tasks == 0 || part), CFM_ERR_ARG, "bad args");
+  CFM_REQUIRE(!scale || (buf && buf->partial_p && buf->rms_out), CFM_ERR_ARG,
+              "scale_parameter without the p^2 partial / RMS buffers");
+  CFM_REQUIRE(dev_table && tot && buf && buf->rowmean && buf->partial && n > 0 &&
+                  (tot->colpart_tasks == 0 || buf->part), CFM_ERR_ARG, "bad args");
   const AdaP* t = reinterpret_cast<const AdaP*>(dev_table);
   hipStream_t s = cfm::as_stream(stream);
-  const float* sc = h->scalars_dev;
-  const float b2t = h->beta2t, eps1 = h->eps1;
-  const dim3 g_cp((unsigned)ncp_tasks), g_rows((unsigned)((nrow_tasks + 3) / 4)),
-      g_cols((unsigned)((ncols + EB - 1) / EB)), g_blk((unsigned)nblocks);
+  const dim3 eb(EB), g_cp((unsigned)tot->colpart_tasks), g_rows((unsigned)((tot->row_tasks + 3) / 4)),
+      g_cols((unsigned)((tot->cols + EB - 1) / EB)), g_rm((unsigned)((tot->rowmean_tasks + 3) / 4)),
+      g_blk((unsigned)tot->blocks);
+  // the passes that read beta2t (statistics, row means, the update's sum of squares): the host's float or the scalars
+  auto moments = [&](auto b2) {
+    using B2 = decltype(b2);
+    if (tot->colpart_tasks > 0)
+      hipLaunchKernelGGL(ada_colpart<B2>, g_cp, eb, 0, s, t, n, tot->colpart_tasks, b2, h->eps1, buf->part);
+    if (tot->row_tasks > 0)
+      hipLaunchKernelGGL(ada_rows<B2>, g_rows, eb, 0, s, t, n, tot->row_tasks, b2, h->eps1);
+    if (tot->cols > 0)
+      hipLaunchKernelGGL(ada_cols<B2>, g_cols, eb, 0, s, t, n, tot->cols, b2, h->eps1, buf->part);
+    if (tot->rowmean_tasks > 0)
+      hipLaunchKernelGGL(ada_rowmean, g_rm, eb, 0, s, t, n, tot->rowmean_tasks, buf->rowmean);
+    if (scale)
+      hipLaunchKernelGGL((ada_sumsq<true, B2>), g_blk, eb, 0, s, t, n, buf->rowmean, b2, h->eps1, buf->partial,
+                         SumsqEx<true>{buf->partial_p});
+    else
+      hipLaunchKernelGGL((ada_sumsq<false, B2>), g_blk, eb, 0, s, t, n, buf->rowmean, b2, h->eps1, buf->partial,
+                         SumsqEx<false>{});
+  };
   if (dev) {
     hipLaunchKernelGGL(ada_scalars, dim3(1), dim3(64), 0, s, h->step_dev, h->scalars_dev, h->decay_rate, h->lr,
                        (int)((h->flags & CFM_ADA_RELATIVE_STEP) != 0), (int)((h->flags & CFM_ADA_WARMUP_INIT) != 0));
-    if (ncp_tasks > 0)
-      hipLaunchKernelGGL(ada_colpart<const float*>, g_cp, dim3(EB), 0, s, t, n, ncp_tasks, sc, eps1, part);
-    if (nrow_tasks > 0) hipLaunchKernelGGL(ada_rows<const float*>, g_rows, dim3(256), 0, s, t, n, nrow_tasks, sc, eps1);
-    if (ncols > 0) hipLaunchKernelGGL(ada_cols<const float*>, g_cols, dim3(EB), 0, s, t, n, ncols, sc, eps1, part);
+    moments(static_cast<const float*>(h->scalars_dev));
   } else {
-    if (ncp_tasks > 0) hipLaunchKernelGGL(ada_colpart<float>, g_cp, dim3(EB), 0, s, t, n, ncp_tasks, b2t, eps1, part);
-    if (nrow_tasks > 0) hipLaunchKernelGGL(ada_rows<float>, g_rows, dim3(256), 0, s, t, n, nrow_tasks, b2t, eps1);
-    if (ncols > 0) hipLaunchKernelGGL(ada_cols<float>, g_cols, dim3(EB), 0, s, t, n, ncols, b2t, eps1, part);
+    moments(h->beta2t);
   }
-  if (nrm_tasks > 0)
-    hipLaunchKernelGGL(ada_rowmean, dim3((unsigned)((nrm_tasks + 3) / 4)), dim3(256), 0, s, t, n, nrm_tasks, rowmean);
-  if (scale && dev)
-    hipLaunchKernelGGL((ada_sumsq<true, const float*>), g_blk, dim3(EB), 0, s, t, n, rowmean, sc, eps1, partial,
-                       SumsqEx<true>{partial_p});
-  else if (scale)
-    hipLaunchKernelGGL((ada_sumsq<true, float>), g_blk, dim3(EB), 0, s, t, n, rowmean, b2t, eps1, partial,
-                       SumsqEx<true>{partial_p});
-  else if (dev)
-    hipLaunchKernelGGL((ada_sumsq<false, const float*>), g_blk, dim3(EB), 0, s, t, n, rowmean, sc, eps1, partial,
-                       SumsqEx<false>{});
-  else
-    hipLaunchKernelGGL((ada_sumsq<false, float>), g_blk, dim3(EB), 0, s, t, n, rowmean, b2t, eps1, partial,
-                       SumsqEx<false>{});
   // (the apply pass does not read beta2t: ada_sumsq has updated the second moments)
-  hipLaunchKernelGGL(ada_apply<true>, g_blk, dim3(EB), 0, s, t, n, rowmean, b2t, eps1, partial, h->lr, h->beta1,
-                     h->clip, ApplyEx<true>{scale ? partial_p : nullptr, dev ? sc : nullptr, rms_out, h->eps2,
-                                            h->weight_decay});
-  return cfm::check_launch("cfm_adafactor_step_ex");
+  if (dev || scale || h->weight_decay != 0.f)     // anything ada_apply<false> does not do
+    hipLaunchKernelGGL(ada_apply<true>, g_blk, eb, 0, s, t, n, buf->rowmean, h->beta2t, h->eps1, buf->partial, h->lr,
+                       h->beta1, h->clip, ApplyEx<true>{scale ? buf->partial_p : nullptr,
+                                                        dev ? h->scalars_dev : nullptr, buf->rms_out, h->eps2,
+                                                        h->weight_decay});
+  else
+    hipLaunchKernelGGL(ada_apply<false>, g_blk, eb, 0, s, t, n, buf->rowmean, h->beta2t, h->eps1, buf->partial, h->lr,
+                       h->beta1, h->clip, ApplyEx<false>{});
+  return cfm::check_launch("cfm_adafactor_step");
 }

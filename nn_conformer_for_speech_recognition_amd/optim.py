@@ -146,13 +146,11 @@ class Adafactor(torch.optim.Optimizer):
         return lr
 
     def _build_table(self, group, ps, dev):
-        """Host-side task table of one group (one ctypes fill per parameter) -> device copy."""
-        lib = L.load()
+        """Host-side task table of one group (one planned fill) -> (device copy, the plan's totals)."""
         n = len(ps)
         host = (ctypes.c_char * L.size_call("cfm_adafactor_table_bytes", n))()
-        row_off = col_off = blk_off = rm_off = rm_toff = cp_off = part_off = 0
+        params = (L.AdafactorParam * n)()
         rms, counter, _ = self._group_buffers(group, dev)
-        steps = []
         for i, p in enumerate(ps):
             st = self._ensure_state(p, group)
             if counter is not None:
@@ -161,28 +159,16 @@ class Adafactor(torch.optim.Optimizer):
                     if torch.is_tensor(st["step"]) or st["step"] != 0 or id(counter) in self._stepped:
                         raise L.CfmError("libcfm Adafactor: all parameters of a group must share the step count")
                     st["step"] = counter
-            else:
-                st["step"] += 1
-                steps.append(st["step"])
             if group["scale_parameter"]:
                 st["RMS"] = rms[i]          # the kernel writes RMS(p) of table entry i here
             factored, nb, R, C = self._geom(p)
             m = st.get("exp_avg")
             row = st["exp_avg_sq_row"] if factored else st["exp_avg_sq"]
             col = st["exp_avg_sq_col"] if factored else None
-            L.call("cfm_adafactor_fill_table", ctypes.cast(host, ctypes.c_void_p), i, L.ptr(p), L.ptr(p.grad),
-                   L.ptr(m), L.ptr(row), L.ptr(col), p.numel(), nb, R, C, row_off, col_off, blk_off, rm_off,
-                   rm_toff, cp_off, part_off)
-            if factored:
-                row_off += lib.cfm_adafactor_row_tasks(nb, R, C)
-                cp_off += lib.cfm_adafactor_colpart_tasks(nb, R, C)
-                part_off += lib.cfm_adafactor_part_floats(nb, R, C)
-                col_off += nb * C
-                rm_off += nb
-                rm_toff += lib.cfm_adafactor_rowmean_tasks(nb, R)
-            blk_off += lib.cfm_adafactor_blocks(p.numel())
-        if counter is None and len(set(steps)) != 1:
-            raise L.CfmError("libcfm Adafactor: all parameters of a group must share the step count")
+            params[i] = L.AdafactorParam(L.ptr(p), L.ptr(p.grad), L.ptr(m), L.ptr(row), L.ptr(col), p.numel(),
+                                         nb, R, C, factored)
+        totals = L.AdafactorTotals()
+        L.call("cfm_adafactor_fill_table", ctypes.cast(host, ctypes.c_void_p), params, n, ctypes.byref(totals))
         raw = bytes(host)
         tkey = (id(group), dev)
         cached = self._tables.get(tkey)
@@ -191,7 +177,7 @@ class Adafactor(torch.optim.Optimizer):
         else:
             table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev, non_blocking=False)
             self._tables[tkey] = (raw, table)
-        return table, (steps[0] if steps else None), (row_off, col_off, blk_off, rm_off, rm_toff, cp_off, part_off)
+        return table, totals
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -215,35 +201,33 @@ class Adafactor(torch.optim.Optimizer):
             ptrkey = self._ptrkey(ps)
             fast = self._fast.get((id(group), dev))
             if fast is not None and fast[0] == ptrkey:
-                table, offs = fast[1], fast[2]
-                step = None
-                if not capturable:      # (capturable: the one device counter, incremented by the step itself)
-                    steps = set()
-                    for p in ps:
-                        st = self.state[p]
-                        st["step"] += 1
-                        steps.add(st["step"])
-                    if len(steps) != 1:
-                        raise L.CfmError("libcfm Adafactor: all parameters of a group must share the step count")
-                    step = steps.pop()
-                row_off, col_off, blk_off, rm_off, rm_toff, cp_off, part_off = offs
+                table, tot = fast[1], fast[2]
             else:
                 if torch.cuda.is_current_stream_capturing():    # no table upload inside a capture
                     raise L.CfmError(_NEEDS_WARMUP)
-                table, step, offs = self._build_table(group, ps, dev)
-                row_off, col_off, blk_off, rm_off, rm_toff, cp_off, part_off = offs
-                self._fast[(id(group), dev)] = (self._ptrkey(ps), table, offs)   # state now exists
+                table, tot = self._build_table(group, ps, dev)
+                self._fast[(id(group), dev)] = (self._ptrkey(ps), table, tot)   # state now exists
+            step = None
+            if not capturable:      # (capturable: the one device counter, incremented by the step itself)
+                steps = set()
+                for p in ps:
+                    st = self.state[p]
+                    st["step"] += 1
+                    steps.add(st["step"])
+                if len(steps) != 1:
+                    raise L.CfmError("libcfm Adafactor: all parameters of a group must share the step count")
+                step = steps.pop()
             key = (id(group), dev)
             buf = self._dev.get(key)
             scale = group["scale_parameter"]
-            if (buf is None or buf[0].numel() < max(rm_off, 1) or buf[1].numel() < max(part_off, 1)
-                    or buf[2].numel() < blk_off or (scale and buf[3] is None)):
-                buf = (torch.empty(max(rm_off, 1), device=dev), torch.empty(max(part_off, 1), device=dev),
-                       torch.empty(max(blk_off, 1), device=dev),
-                       torch.empty(max(blk_off, 1), device=dev) if scale else None)     # block sums of p^2
+            if (buf is None or buf[0].numel() < tot.rowmean_floats or buf[1].numel() < tot.part_floats
+                    or buf[2].numel() < tot.blocks or (scale and buf[3] is None)):
+                buf = (torch.empty(max(tot.rowmean_floats, 1), device=dev),
+                       torch.empty(max(tot.part_floats, 1), device=dev), torch.empty(max(tot.blocks, 1), device=dev),
+                       torch.empty(max(tot.blocks, 1), device=dev) if scale else None)     # block sums of p^2
                 self._dev[key] = buf
             beta1 = group["beta1"] if group["beta1"] is not None else 0.0
-            # (scale_parameter=False, weight_decay=0, not capturable: the library makes cfm_adafactor_step's launches)
+            # (scale_parameter=False, weight_decay=0, not capturable: the six launches of the reference's step)
             rms, counter, scalars = self._group_buffers(group, dev)
             h = L.AdafactorHyper(decay_rate=group["decay_rate"], beta1=beta1, eps1=group["eps"][0],
                                  eps2=group["eps"][1], clip=group["clip_threshold"],
@@ -257,8 +241,8 @@ class Adafactor(torch.optim.Optimizer):
             else:
                 h.lr = self._lr(group, step)
                 h.beta2t = 1.0 - math.pow(step, group["decay_rate"])
-            L.call("cfm_adafactor_step_ex", L.ptr(table), n, row_off, col_off, blk_off, rm_toff, cp_off,
-                   L.ptr(buf[0]), L.ptr(buf[1]), L.ptr(buf[2]), L.ptr(buf[3]), L.ptr(rms), ctypes.byref(h),
+            bufs = L.AdafactorBuffers(*map(L.ptr, buf), L.ptr(rms))
+            L.call("cfm_adafactor_step", L.ptr(table), n, ctypes.byref(tot), ctypes.byref(bufs), ctypes.byref(h),
                    L.stream())
             self._keep = table      # keep the table alive until the stream has consumed it
         return loss
