@@ -980,6 +980,39 @@ int cfm_ctc_nbest_bwd(const float* logits, long sb, long st, const int32_t* in_l
                       const int32_t* hyp, int ldh, const int32_t* hyp_len, int N, int max_labels, int blank, void* ws,
                       const float* grad_loss, int grad_stride, float* grad_logits, long gsb, long gst, void* stream);
 
+/* RNN-T (transducer) loss over a dense lattice of joint logits, and its gradient (Graves 2012; the interface of
+ * torchaudio.functional.rnnt_loss).  The reference has no counterpart.  logits (B, T, U1, V) fp32, dense, U1 = Umax + 1
+ * (log-softmax over V is applied); targets int32, row b at targets + b * ldt, ldt >= U1 - 1, holding no blanks
+ * (NULL allowed when U1 == 1); in_len, tgt_len (B) int32 on the device, clamped there to [0, T] and [0, U1 - 1], the
+ * labels to [0, V - 1], never read back: a bad value can give a wrong answer, never an access outside a buffer.
+ * With T_b, U_b the clamped lengths, lp = log_softmax(logits), b(t,u) = lp[t,u,blank], y(t,u) = lp[t,u,label_{u+1}]:
+ *   alpha(0,0) = 0;  alpha(t,u) = lse(alpha(t-1,u) + b(t-1,u), alpha(t,u-1) + y(t,u-1))
+ *   beta(T_b-1,U_b) = b(T_b-1,U_b);  beta(t,u) = lse(beta(t+1,u) + b(t,u), beta(t,u+1) + y(t,u))
+ *   ll[b] = alpha(T_b-1,U_b) + b(T_b-1,U_b) (= beta(0,0)), natural log; the loss is -ll[b]
+ *   ll[b] = -inf when T_b == 0 (the utterance takes no part) or when the value is not finite
+ * cfm_rnnt_loss_bwd after cfm_rnnt_loss_fwd, same arguments and the same ws untouched in between; with
+ * gamma(t,u) = exp(alpha + beta - ll), for the valid cells t < T_b, u <= U_b:
+ *   dlogits[b,t,u,v] = grad_loss[b] * ( softmax(logits)[b,t,u,v] * gamma(t,u)
+ *                      - [v == blank] exp(alpha(t,u) + b(t,u) + beta(t+1,u) - ll)      (at (T_b-1, U_b): gamma)
+ *                      - [v == label_{u+1}, u < U_b] exp(alpha(t,u) + y(t,u) + beta(t,u+1) - ll) )
+ * the gradient of sum_b grad_loss[b] * (-ll[b]).  Every valid row of it sums to 0 over v (beta(t,u) is the log-sum of
+ * the two subtracted exponents).  Outside the valid cells, and for an utterance with ll = -inf, the rows are exact
+ * zeros: the whole dlogits buffer is written, and the logits outside the valid cells are never read.
+ * alpha, beta and ll are double with fp32 exp / log on O(1) differences (csrc/ctc_nbest.hip, "Precision").
+ * B, T, U1, V > 0 and ldt >= U1 - 1 (CFM_ERR_SHAPE); non-null pointers and 0 <= blank < V (CFM_ERR_ARG); U1 <= 1024,
+ * V >= 2 and B * T * U1 < 2^31 (CFM_ERR_UNSUPPORTED); ws: cfm_rnnt_ws_bytes(B, T, U1) bytes, 8-byte aligned
+ * (CFM_ERR_ALIGN): per cell of the (T + U1 - 1) x U1 diagonal-major lattice two doubles (alpha, beta) and two floats
+ * (b, y), plus a float per logits row.  Forward: two launches (emissions: the only pass over the logits; alpha and
+ * beta side by side, the alpha block writing ll); backward: one.  No host synchronisation
+ * (graph-capturable), no wait on another wave's progress, no atomics: results are bit-identical from run to run. */
+size_t cfm_rnnt_ws_bytes(int B, int T, int U1);
+int cfm_rnnt_loss_fwd(const float* logits, const int32_t* targets, int ldt, const int32_t* in_len,
+                      const int32_t* tgt_len, int B, int T, int U1, int V, int blank, float* ll, void* ws,
+                      void* stream);
+int cfm_rnnt_loss_bwd(const float* logits, const int32_t* targets, int ldt, const int32_t* in_len,
+                      const int32_t* tgt_len, int B, int T, int U1, int V, int blank, const void* ws,
+                      const float* grad_loss, float* dlogits, void* stream);
+
 /* Batched edit distance (Levenshtein) over token ids: the numerator of the word error rate -- the vocabulary's tokens
  * are words -- in place of the host loop of jiwer's wer (reference runner.py:160,230), and the aligned pairs the
  * reference's confusion matrix is built from (evals.py:64).  Pair p < P compares hypothesis row p (hyp + p * ldh,

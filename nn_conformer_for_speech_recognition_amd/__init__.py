@@ -8,3 +8,4 @@ libcfm.so behind the C ABI in include/cfm.h.
 __version__ = "0.1.0"
 
 from . import library  # noqa: E402,F401  (registers torch.ops.cfm.*)
+from . import transducer  # noqa: E402,F401  (rnnt_loss, TransducerHead)

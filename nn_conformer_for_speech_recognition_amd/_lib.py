@@ -342,6 +342,13 @@ _SIGS = {
     "cfm_ctc_nbest_bwd": (c_int, [c_void_p, c_long, c_long, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                                   c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_long, c_long,
                                   c_void_p]),
+    "cfm_rnnt_ws_bytes": (c_size_t, [c_int, c_int, c_int]),   # (B, T, U1)
+    # (logits, targets, ldt, in_len, tgt_len, B, T, U1, V, blank, ll, ws, stream)
+    "cfm_rnnt_loss_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                  c_void_p, c_void_p, c_void_p]),
+    # (the same through blank, ws, grad_loss, dlogits, stream)
+    "cfm_rnnt_loss_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "cfm_edit_distance_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),   # (P, Rmax, Hmax, want_ops)
     # (ref, ldr, ref_len, n_ref, hyp, ldh, hyp_len, P, group, Rmax, Hmax, dist, counts, pair_ref, pair_hyp, ldp,
     #  n_pairs, ws, stream)

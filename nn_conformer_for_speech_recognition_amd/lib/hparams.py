@@ -41,6 +41,11 @@ MI355X build (documented in DESIGN.md):
                                            expected word errors over the beam's mwer_nbest best hypotheses
                                            (ctc.mwer_loss; beam width max(beam_size, mwer_nbest)); history["loss"]
                                            stays the CTC loss, history["mwer"] records the term
+  transducer_weight      float | None      None: no transducer head (the model and the step unchanged).  A number
+  transducer_embed,      int               (set_transducer, BEFORE the model is built): ASRNN adds
+  transducer_hidden,                       transducer.TransducerHead on the encoder output and Runner.train minimises
+  transducer_joint                         ctc + transducer_weight * sum_b(rnnt_b) / batch_size; history["rnnt"]
+                                           records the term, decoding stays with the CTC head
 """
 from __future__ import annotations
 
@@ -87,7 +92,8 @@ _NST_LM = dict(nst=True, lm=False, train_lm=False, ft_lr=3e-6, ft_epochs=3, ft_t
 _BUILD = dict(compute_dtype="bf16", frontend_proj="utterance", pos_enc="none", use_group_norm=False,
               specaug_ref_noop_masks=False, dp_world_size=1, layer_norm_eps=1e-5, bn_eps=1e-5, bn_momentum=0.1, beam_size=0,
               decoder_lm=None, lm_weight=0.0, word_bonus=0.0, token_beam=0, nst_min_confidence=None,
-              decoder_batched=False, device_wer=False, mwer_weight=None, mwer_nbest=4)
+              decoder_batched=False, device_wer=False, mwer_weight=None, mwer_nbest=4, transducer_weight=None,
+              transducer_embed=128, transducer_hidden=256, transducer_joint=256)
 
 
 class HParams:
@@ -179,6 +185,22 @@ class HParams:
         self.mwer_nbest = int(nbest)
         if not 1 <= self.mwer_nbest <= 128:
             raise ValueError(f"mwer nbest must be in [1, 128], got {nbest}")
+
+    def set_transducer(self, weight, embed=128, hidden=256, joint=256):
+        """A transducer head beside the CTC head (transducer.TransducerHead on the encoder output, taken before the
+        BiLSTM decoder): with weight a number, ASRNN builds the head as model.transducer and Runner.train minimises
+        ctc + weight * sum_b(rnnt_b) / batch_size, rnnt_b the RNN-T loss of utterance b (transducer.rnnt_loss).
+        history["loss"] stays the CTC loss alone; history["rnnt"] records the term.  The metric, the label pass and
+        test keep decoding with the CTC head.  A MODEL option like use_group_norm: set it before the model is built
+        (the head adds parameters to the state dict).  None (the default): no head, the model and the step unchanged.
+        embed / hidden / joint: the prediction network's embedding and LSTM widths (hidden a multiple of 8, at most
+        1024: lstm.LSTM) and the joint network's width."""
+        self.transducer_weight = None if weight is None else float(weight)
+        self.transducer_embed, self.transducer_hidden, self.transducer_joint = int(embed), int(hidden), int(joint)
+        if self.transducer_hidden % 8 or not 8 <= self.transducer_hidden <= 1024:
+            raise ValueError(f"transducer hidden must be a multiple of 8 in [8, 1024], got {hidden}")
+        if self.transducer_embed < 1 or self.transducer_joint < 1:
+            raise ValueError("transducer embed and joint must be positive")
 
     def set_ntokens(self, ntokens):
         self.ntokens = ntokens

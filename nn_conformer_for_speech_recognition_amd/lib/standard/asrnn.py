@@ -26,6 +26,7 @@ from ...ctc import beam_search_decode as _beam_search_decode, forced_align as _f
     greedy_decode as _greedy_decode
 from ...frontend import frame_frontend as _frame_frontend, linear as _linear, projection_block as _projection_block
 from ...lstm import LSTM
+from ...transducer import TransducerHead
 from ..convsubsampling import ConvSubSampling
 
 _DTYPES = {"bf16": torch.bfloat16, "fp32": torch.float32, torch.bfloat16: torch.bfloat16,
@@ -73,6 +74,12 @@ class ASRNN(nn.Module):
         self.beta = torch.rand(1).to(hp.device)
         self.beta.requires_grad = True
         self.log_softmax = nn.LogSoftmax(-1)
+        # hp.transducer_weight set (HParams.set_transducer): the transducer head on the encoder output.  Built LAST, so
+        # that every other parameter's initial value for a given seed is the one it has without the head.
+        if getattr(hp, "transducer_weight", None) is not None:
+            self.transducer = TransducerHead(hp.projection_out_size, hp.ntokens, int(hp.blank_idx),
+                                             embed=hp.transducer_embed, hidden=hp.transducer_hidden,
+                                             joint=hp.transducer_joint)
 
     # ------------------------------------------------------------------ reference surface
     def predict(self, x):
@@ -201,8 +208,12 @@ class ASRNN(nn.Module):
         lens = nn.functional.pad(lens, (0, B - lens.shape[0]))
         return lens.clamp(0, T_enc).to(torch.int32)
 
-    def forward(self, x, input_lens, SpecAugment=False, lm=None, finetuning=False):
+    def forward(self, x, input_lens, SpecAugment=False, lm=None, finetuning=False, return_encoder=False):
         """asrnn.py:237-259: (B, F, T) mels -> log-probs (B, T_enc, ntokens), output lengths.
+
+        return_encoder: a third result, (the encoder output as a (B, T_enc, projection_out_size) view, taken before the
+        BiLSTM decoder; its frames per utterance, decoder_lengths()) -- what the transducer head (self.transducer,
+        HParams.set_transducer) takes.  The default returns the two values above.
 
         hp.decoder_batched: the BiLSTM decoder gets the encoder output as a (B, T_enc, .) view and
         decoder_lengths() as lengths, so every utterance is a sequence of its own from a zero state (its output
@@ -212,6 +223,9 @@ class ASRNN(nn.Module):
         B = x.shape[0]
         x = x.unsqueeze(1)
         x, output_lens = self.encoder(x, input_lens, SpecAugment, finetuning=finetuning)
+        if return_encoder:
+            enc = x.view(B, x.shape[0] // B, x.shape[1])
+            enc_lens = self.decoder_lengths(output_lens.to(x.device), B, enc.shape[1])
         if getattr(self.hp, "decoder_batched", False):
             T_enc = x.shape[0] // B
             lens = self.decoder_lengths(output_lens.to(x.device), B, T_enc)
@@ -224,4 +238,6 @@ class ASRNN(nn.Module):
         x = self.log_softmax(x)
         if lm is not None:
             x = x + lm(self.hp.ngram, torch.argmax(x, -1))
+        if return_encoder:
+            return x, output_lens, (enc, enc_lens)
         return x, output_lens

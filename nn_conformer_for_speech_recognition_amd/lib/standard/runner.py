@@ -32,6 +32,11 @@ Same constructor, methods and control flow as the reference; what runs underneat
                ctc + weight * mean_b(mwer_b), mwer_b = ctc.mwer_loss: the expected word errors over the beam's
                hp.mwer_nbest best hypotheses of the step's own logits (no reference counterpart).  history["loss"] stays
                the CTC loss; history["mwer"] holds the epoch's mean of the term, accumulated on the device.
+  transducer   hp.transducer_weight (default None: no head, the step unchanged; HParams.set_transducer, before the model
+               is built): train minimises ctc + weight * sum_b(rnnt_b) / batch_size, rnnt_b = the RNN-T loss of
+               model.transducer (transducer.TransducerHead) on the encoder output (no reference counterpart).
+               history["loss"] stays the CTC loss; history["rnnt"] holds the epoch's mean of the term, accumulated on
+               the device.  The metric, the label pass and test keep decoding with the CTC head.
 
 Dropped (outside the hot path): tqdm colours, Evals plots (losses / WER are kept on
 the Runner as .history and written to hp.plots_dir/history.json), the transformer-LM weight fusion (fuse_models).
@@ -141,6 +146,18 @@ class Runner:
                                blank=voc.blank_idx, pad=voc.pad_idx, max_labels=min(T, 511), **kw)
         return loss.sum() / self.hp.batch_size
 
+    def _rnnt(self, encoder, target, target_lens, lengths):
+        """hp.transducer_weight set: sum over the rows of the model's transducer loss on the step's encoder output
+        (attached) / hp.batch_size, over the first min(rows of the encoder output, rows of target) rows, as _mwer.
+        A row's frames are the encoder's (ASRNN.decoder_lengths), and none where the step's padded length vector
+        `lengths` has none (the rows that pad a short last batch): such rows, and losses that are not finite,
+        contribute 0 (zero_infinity).  Nothing is read back."""
+        enc, enc_lens = encoder
+        n = min(enc.shape[0], target.shape[0])
+        frames = torch.where(lengths[:n] > 0, enc_lens[:n], torch.zeros_like(enc_lens[:n]))
+        loss = self.model.transducer(enc[:n], frames, target[:n], target_lens[:n], zero_infinity=True)
+        return loss.sum() / self.hp.batch_size
+
     def _beam_labels(self, voc, logits, lengths, confidence=False):
         """hp.beam_size > 0: the best prefix-beam-search hypothesis per utterance as label strings (lengths: the
         model's output lengths, padded / truncated to the batch; the kernel clamps them to [0, T]).  confidence (the
@@ -239,6 +256,10 @@ class Runner:
         want_wer = getattr(self.hp, "train_wer", True)     # WER forces a host sync per step
         device_wer = bool(getattr(self.hp, "device_wer", False))
         mwer_weight = getattr(self.hp, "mwer_weight", None)     # None: the CTC loss alone (HParams.set_mwer)
+        rnnt_weight = getattr(self.hp, "transducer_weight", None)     # None: no transducer term (set_transducer)
+        if rnnt_weight is not None and not hasattr(self.model, "transducer"):
+            raise ValueError("hp.transducer_weight is set but the model has no transducer head: call "
+                             "HParams.set_transducer before the model is built")
         for _ in range(epochs):
             self.model.train()
             train_set.shuffle(dataset_type)
@@ -246,12 +267,18 @@ class Runner:
             acc = self._new_accumulator() if device_wer else None
             if mwer_weight is not None:     # the epoch's sum of the MWER term, on the device, read once
                 mwer_sum = torch.zeros((), dtype=torch.float64, device=self.hp.device)
+            if rnnt_weight is not None:     # the epoch's sum of the transducer term, on the device, read once
+                rnnt_sum = torch.zeros((), dtype=torch.float64, device=self.hp.device)
             for i in range(train_size):
                 batch = train_set.get_batch(i, dataset_type)
                 inbatch, input_lens = batch["input"]["mels"], batch["input"]["tau"]
                 target, target_lens = batch["target"]["transcripts"], batch["target"]["lens"]
                 self.optimizer.zero_grad()
-                logits, output_lengths = self.model(inbatch, input_lens, SpecAugment, finetuning=finetuning)
+                if rnnt_weight is not None:
+                    logits, output_lengths, encoder = self.model(inbatch, input_lens, SpecAugment,
+                                                                 finetuning=finetuning, return_encoder=True)
+                else:
+                    logits, output_lengths = self.model(inbatch, input_lens, SpecAugment, finetuning=finetuning)
                 output_lengths = nn.functional.pad(output_lengths, (0, self.hp.batch_size - output_lengths.shape[0]))
                 output_lengths = output_lengths.clamp(max=logits.shape[1])
                 loss = self.loss(logits.transpose(0, 1), target, output_lengths, target_lens)
@@ -260,6 +287,10 @@ class Runner:
                     mwer = self._mwer(train_set.vocab, logits, target, target_lens, output_lengths)
                     objective = loss + mwer_weight * mwer
                     mwer_sum += mwer.detach().double()
+                if rnnt_weight is not None:     # ... + weight * sum_b(rnnt_b) / batch_size
+                    rnnt = self._rnnt(encoder, target, target_lens, output_lengths)
+                    objective = objective + rnnt_weight * rnnt
+                    rnnt_sum += rnnt.detach().double()
                 if device_wer:     # loss and word errors stay on the device: no host sync in the step
                     objective.backward()
                     self.optimizer.step()
@@ -284,6 +315,8 @@ class Runner:
                 self.history["metric"].append(mean(emetric) if emetric else float("nan"))
             if mwer_weight is not None:
                 self.history.setdefault("mwer", []).append(mwer_sum.item() / train_size if train_size else float("nan"))
+            if rnnt_weight is not None:
+                self.history.setdefault("rnnt", []).append(rnnt_sum.item() / train_size if train_size else float("nan"))
             if "validation" in train_set.idxes:
                 vl, vm = self.test(train_set, "validation", finetuning=finetuning)
                 self.history["val_loss"].append(vl)

@@ -1180,6 +1180,29 @@ def ctc_nbest_bwd(x, in_len_i32, hyp_i32, ldh, hyp_len_i32, N, max_labels, blank
     return g
 
 
+def rnnt_loss_fwd(x, targets_i32, ldt, in_len_i32, tgt_len_i32, blank):
+    """RNN-T log-likelihoods of dense joint logits x (B, T, U1, V) fp32 contiguous (cfm_rnnt_loss_fwd): utterance b's
+    labels are row targets_i32 + b * ldt.  -> (ll (B,) fp32: -inf where the utterance takes no part, ws for
+    rnnt_loss_bwd)."""
+    B, T, U1, V = x.shape
+    ll = torch.empty(B, device=x.device, dtype=torch.float32)
+    ws = workspace(L.size_call("cfm_rnnt_ws_bytes", B, T, U1), x.device)
+    L.call("cfm_rnnt_loss_fwd", L.ptr(x), L.ptr(targets_i32) or None, int(ldt), L.ptr(in_len_i32), L.ptr(tgt_len_i32),
+           B, T, U1, V, int(blank), L.ptr(ll), L.ptr(ws), L.stream())
+    return ll, ws
+
+
+def rnnt_loss_bwd(x, targets_i32, ldt, in_len_i32, tgt_len_i32, blank, ws, grad_loss):
+    """d (sum_b grad_loss[b] * -ll[b]) / d x of rnnt_loss_fwd (cfm_rnnt_loss_bwd), fp32 (B, T, U1, V): every row
+    written, exact zeros outside the valid cells."""
+    B, T, U1, V = x.shape
+    g = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    go = grad_loss.float().contiguous()
+    L.call("cfm_rnnt_loss_bwd", L.ptr(x), L.ptr(targets_i32) or None, int(ldt), L.ptr(in_len_i32), L.ptr(tgt_len_i32),
+           B, T, U1, V, int(blank), L.ptr(ws), L.ptr(go), L.ptr(g), L.stream())
+    return g
+
+
 def edit_distance(ref_i32, ldr, ref_len_i32, hyp_i32, ldh, hyp_len_i32, P, group, rmax, hmax, want_ops=False,
                   out=None):
     """Batched edit distance over token ids (cfm_edit_distance): pair p compares hypothesis row p (hyp_i32 + p * ldh)
