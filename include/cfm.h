@@ -1013,6 +1013,31 @@ int cfm_rnnt_loss_bwd(const float* logits, const int32_t* targets, int ldt, cons
                       const int32_t* tgt_len, int B, int T, int U1, int V, int blank, const void* ws,
                       const float* grad_loss, float* dlogits, void* stream);
 
+/* Time-synchronous greedy search of a transducer head (transducer.TransducerHead), one launch, one workgroup per
+ * utterance (csrc/rnnt_greedy.hip).  The reference has no counterpart.  All fp32, contiguous: ep (B, T, J) =
+ * enc_proj(enc) with bias; gtab (V, 4H) = embedding.weight W_ih^T + b_ih + b_hh (the LSTM cell's input half of token
+ * v is row v); w_hh (4H, H); w_pp (J, H), b_pp (J): pred_proj; w_out (V, J), b_out (V): out.  lengths (B) int32 on the
+ * device, clamped there to [0, T] and never read back, or NULL (T).  Per utterance, T_b the clamped length:
+ *   (h, c) = cell(0, 0, gtab[blank]);  pp = w_pp h + b_pp
+ *   for t < T_b, at most max_symbols times:
+ *     logits = w_out tanh(ep[b,t] + pp) + b_out;  tok = argmax, ties to the LOWEST index (torch's rule)
+ *     scores[b] += log_softmax(logits)[tok], formed as (x - m) - log sum exp(x - m), accumulated in double
+ *     tok == blank: the frame is closed.  Otherwise tok is emitted at frame t (an utterance that has emitted W
+ *     tokens stops there), (h, c) = cell(h, c, gtab[tok]) -- gates = gtab[tok] + w_hh h, order i, f, g, o,
+ *     c = sigmoid(f) c + sigmoid(i) tanh(g), h = sigmoid(o) tanh(c) -- and pp is recomputed.
+ * A frame closed by the max_symbols cap adds no blank term to the score.
+ * Outputs, every element written: tokens (B, W) and frames (B, W) int32 padded with -1 (frames: the frame each token
+ * was emitted at), counts (B) int32, scores (B) fp32.
+ * A logit's operation order depends on neither its row nor the utterance's place in the batch: identical rows of w_out
+ * with identical biases give bit-equal logits.  No communication between workgroups, no atomics, no spin; trip counts
+ * are bounded by T_b * max_symbols; no host synchronisation (graph-capturable); results are bit-identical from run to
+ * run.  B, T, V, H, J, W > 0 (CFM_ERR_SHAPE); non-null pointers (lengths excepted), 0 <= blank < V and
+ * max_symbols >= 1 (CFM_ERR_ARG); V >= 2, H <= 1024 with H % 8 == 0, J <= 1024 (CFM_ERR_UNSUPPORTED): no launch. */
+int cfm_rnnt_greedy(const float* ep, const float* gtab, const float* w_hh, const float* w_pp, const float* b_pp,
+                    const float* w_out, const float* b_out, const int32_t* lengths, int B, int T, int V, int H, int J,
+                    int blank, int max_symbols, int W, int32_t* tokens, int32_t* frames, int32_t* counts,
+                    float* scores, void* stream);
+
 /* Batched edit distance (Levenshtein) over token ids: the numerator of the word error rate -- the vocabulary's tokens
  * are words -- in place of the host loop of jiwer's wer (reference runner.py:160,230), and the aligned pairs the
  * reference's confusion matrix is built from (evals.py:64).  Pair p < P compares hypothesis row p (hyp + p * ldh,

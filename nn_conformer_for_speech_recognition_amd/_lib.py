@@ -349,6 +349,9 @@ _SIGS = {
     # (the same through blank, ws, grad_loss, dlogits, stream)
     "cfm_rnnt_loss_bwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    # (ep, gtab, w_hh, w_pp, b_pp, w_out, b_out, lengths, B, T, V, H, J, blank, max_symbols, W, tokens, frames, counts,
+    #  scores, stream)
+    "cfm_rnnt_greedy": (c_int, [c_void_p] * 8 + [c_int] * 8 + [c_void_p] * 5),
     "cfm_edit_distance_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),   # (P, Rmax, Hmax, want_ops)
     # (ref, ldr, ref_len, n_ref, hyp, ldh, hyp_len, P, group, Rmax, Hmax, dist, counts, pair_ref, pair_hyp, ldp,
     #  n_pairs, ws, stream)

@@ -45,7 +45,12 @@ MI355X build (documented in DESIGN.md):
   transducer_embed,      int               (set_transducer, BEFORE the model is built): ASRNN adds
   transducer_hidden,                       transducer.TransducerHead on the encoder output and Runner.train minimises
   transducer_joint                         ctc + transducer_weight * sum_b(rnnt_b) / batch_size; history["rnnt"]
-                                           records the term, decoding stays with the CTC head
+                                           records the term, decoding stays with the CTC head unless:
+  transducer_decode      bool              False: the Runner's metric, test and label passes decode with the CTC head.
+  transducer_max_symbols int               True (set_transducer_decode): they decode with the transducer head's
+                                           greedy search on the encoder output (TransducerHead.decode, one kernel
+                                           launch), at most transducer_max_symbols tokens per frame; needs the head,
+                                           beam_size 0 and no nst_min_confidence; test's loss stays the CTC loss
 """
 from __future__ import annotations
 
@@ -93,7 +98,8 @@ _BUILD = dict(compute_dtype="bf16", frontend_proj="utterance", pos_enc="none", u
               specaug_ref_noop_masks=False, dp_world_size=1, layer_norm_eps=1e-5, bn_eps=1e-5, bn_momentum=0.1, beam_size=0,
               decoder_lm=None, lm_weight=0.0, word_bonus=0.0, token_beam=0, nst_min_confidence=None,
               decoder_batched=False, device_wer=False, mwer_weight=None, mwer_nbest=4, transducer_weight=None,
-              transducer_embed=128, transducer_hidden=256, transducer_joint=256)
+              transducer_embed=128, transducer_hidden=256, transducer_joint=256, transducer_decode=False,
+              transducer_max_symbols=2)
 
 
 class HParams:
@@ -191,7 +197,8 @@ class HParams:
         BiLSTM decoder): with weight a number, ASRNN builds the head as model.transducer and Runner.train minimises
         ctc + weight * sum_b(rnnt_b) / batch_size, rnnt_b the RNN-T loss of utterance b (transducer.rnnt_loss).
         history["loss"] stays the CTC loss alone; history["rnnt"] records the term.  The metric, the label pass and
-        test keep decoding with the CTC head.  A MODEL option like use_group_norm: set it before the model is built
+        test keep decoding with the CTC head (set_transducer_decode switches them to this head).  A MODEL option
+        like use_group_norm: set it before the model is built
         (the head adds parameters to the state dict).  None (the default): no head, the model and the step unchanged.
         embed / hidden / joint: the prediction network's embedding and LSTM widths (hidden a multiple of 8, at most
         1024: lstm.LSTM) and the joint network's width."""
@@ -201,6 +208,19 @@ class HParams:
             raise ValueError(f"transducer hidden must be a multiple of 8 in [8, 1024], got {hidden}")
         if self.transducer_embed < 1 or self.transducer_joint < 1:
             raise ValueError("transducer embed and joint must be positive")
+
+    def set_transducer_decode(self, flag, max_symbols=2):
+        """True: the Runner's metric (train and test, host WER, device_wer and the confusion matrix) and
+        generate_labels decode with the transducer head instead of the CTC head: the model is called with
+        return_encoder=True and model.transducer.decode (the device greedy search, at most max_symbols tokens per
+        frame, the encoder's frame counts as lengths) gives the token ids that Vocab.decode / ctc.edit_distance take.
+        The loss test reports stays the CTC loss.  Needs a model built with set_transducer, beam_size 0 (it would be
+        unclear which head decodes) and nst_min_confidence None (that confidence is a CTC alignment score): the
+        Runner raises ValueError otherwise.  False (the default): every pass as before."""
+        self.transducer_decode = bool(flag)
+        self.transducer_max_symbols = int(max_symbols)
+        if self.transducer_max_symbols < 1:
+            raise ValueError(f"transducer max_symbols must be >= 1, got {max_symbols}")
 
     def set_ntokens(self, ntokens):
         self.ntokens = ntokens

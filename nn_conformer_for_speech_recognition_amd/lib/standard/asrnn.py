@@ -193,6 +193,14 @@ class ASRNN(nn.Module):
             out = self.projection_block(self.dropout(out), True)
         return out, output_lens
 
+    def predict_transducer(self, enc, enc_lengths, max_symbols=2, max_tokens=None):
+        """Greedy search of the transducer head (HParams.set_transducer) on the encoder output enc (B, T_enc, .) with
+        enc_lengths frames per utterance -- forward(..., return_encoder=True)'s third result -> transducer.RNNTGreedy
+        (tokens (B, W) int32 padded with -1, counts, frames, scores); TransducerHead.decode, one kernel launch."""
+        if not hasattr(self, "transducer"):
+            raise ValueError("the model has no transducer head: call HParams.set_transducer before the model is built")
+        return self.transducer.decode(enc, enc_lengths, max_symbols=max_symbols, max_tokens=max_tokens)
+
     def decoder(self, y):
         raise NotImplementedError("ASRNN.decoder is dead code in the reference (asrnn.py:223-236 uses "
                                   "undefined decoder_fc/relu)")

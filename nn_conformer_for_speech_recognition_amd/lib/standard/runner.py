@@ -36,7 +36,14 @@ Same constructor, methods and control flow as the reference; what runs underneat
                is built): train minimises ctc + weight * sum_b(rnnt_b) / batch_size, rnnt_b = the RNN-T loss of
                model.transducer (transducer.TransducerHead) on the encoder output (no reference counterpart).
                history["loss"] stays the CTC loss; history["rnnt"] holds the epoch's mean of the term, accumulated on
-               the device.  The metric, the label pass and test keep decoding with the CTC head.
+               the device.  The metric, the label pass and test keep decoding with the CTC head, unless:
+  transducer   hp.transducer_decode (default False; HParams.set_transducer_decode): the metric of train and test (host
+  decode       WER, device_wer, the confusion matrix) and generate_labels take their token ids from
+               model.transducer.decode -- the device greedy search of the transducer head (csrc/rnnt_greedy.hip, one
+               launch per batch, at most hp.transducer_max_symbols tokens per frame) on the encoder output, the
+               encoder's frame counts as lengths and none for the rows that pad a short last batch -- and feed them to
+               the same Vocab.decode / ctc.edit_distance code.  The loss test reports stays the CTC loss.  Needs the
+               head, hp.beam_size 0 and hp.nst_min_confidence None (ValueError at the start of the pass).
 
 Dropped (outside the hot path): tqdm colours, Evals plots (losses / WER are kept on
 the Runner as .history and written to hp.plots_dir/history.json), the transformer-LM weight fusion (fuse_models).
@@ -52,7 +59,7 @@ from statistics import mean
 import torch
 import torch.nn as nn
 
-from ...ctc import CTCLoss, beam_search_decode, edit_distance, forced_align, greedy_decode, mwer_loss
+from ...ctc import EDIT_MAX_LEN, CTCLoss, beam_search_decode, edit_distance, forced_align, greedy_decode, mwer_loss
 from ...optim import Adafactor
 from .myvocab import wer
 
@@ -158,6 +165,37 @@ class Runner:
         loss = self.model.transducer(enc[:n], frames, target[:n], target_lens[:n], zero_infinity=True)
         return loss.sum() / self.hp.batch_size
 
+    def _transducer_decode_on(self):
+        """hp.transducer_decode, checked against what it needs (the start of train / test / generate_labels)."""
+        if not getattr(self.hp, "transducer_decode", False):
+            return False
+        if not hasattr(self.model, "transducer"):
+            raise ValueError("hp.transducer_decode is set but the model has no transducer head: call "
+                             "HParams.set_transducer before the model is built")
+        if getattr(self.hp, "beam_size", 0) > 0:
+            raise ValueError("hp.transducer_decode with hp.beam_size > 0: the beam search decodes with the CTC head, "
+                             "so it would be unclear which head the metric and the labels come from")
+        if getattr(self.hp, "nst_min_confidence", None) is not None:
+            raise ValueError("hp.transducer_decode with hp.nst_min_confidence: that confidence is the score of a CTC "
+                             "alignment and says nothing about a transducer hypothesis")
+        return True
+
+    def _transducer_tokens(self, encoder, lengths=None):
+        """hp.transducer_decode: (tokens (B, W) int32 padded with -1, counts (B,)) of the transducer head's greedy
+        search on the step's encoder output.  A row's frames follow _rnnt's rule: the encoder's
+        (ASRNN.decoder_lengths), and none where the step's length vector `lengths` (padded with zeros to the batch)
+        has none.  W = min(T * max_symbols, ctc.EDIT_MAX_LEN), so that edit_distance's width limit holds at any T.
+        Nothing is read back."""
+        enc, enc_lens = encoder
+        B, T = enc.shape[:2]
+        frames = enc_lens
+        if lengths is not None:
+            lengths = nn.functional.pad(lengths[:B].to(enc_lens.device), (0, max(0, B - lengths.shape[0])))
+            frames = torch.where(lengths > 0, enc_lens, torch.zeros_like(enc_lens))
+        ms = int(getattr(self.hp, "transducer_max_symbols", 2))
+        out = self.model.transducer.decode(enc, frames, max_symbols=ms, max_tokens=min(T * ms, EDIT_MAX_LEN))
+        return out.tokens, out.counts
+
     def _beam_labels(self, voc, logits, lengths, confidence=False):
         """hp.beam_size > 0: the best prefix-beam-search hypothesis per utterance as label strings (lengths: the
         model's output lengths, padded / truncated to the batch; the kernel clamps them to [0, T]).  confidence (the
@@ -181,7 +219,11 @@ class Runner:
         score = forced_align(logits, toks[:, :smax].clamp(min=0), frames, cnt, blank=voc.blank_idx).score
         return (score / frames.clamp(min=1)).tolist()
 
-    def _metric(self, dataset, logits, target, lengths=None):
+    def _metric(self, dataset, logits, target, lengths=None, encoder=None):
+        if encoder is not None:     # hp.transducer_decode: the transducer head's hypothesis
+            toks, cnt = self._transducer_tokens(encoder, lengths)
+            tw, pw = _word_lists(dataset.vocab.decode(target), dataset.vocab.decode(toks, cnt))
+            return wer(tw, pw) * 100 if tw else 0.0
         if getattr(self.hp, "beam_size", 0) > 0:
             tw, pw = _word_lists(dataset.vocab.decode(target), self._beam_labels(dataset.vocab, logits, lengths))
             return wer(tw, pw) * 100 if tw else 0.0
@@ -192,13 +234,16 @@ class Runner:
         return wer(tw, pw) * 100 if tw else 0.0
 
     # ----------------------------------------------------------------------------- device metric (hp.device_wer)
-    def _edit_distance(self, dataset, logits, target, target_lens, lengths=None, ops=False):
+    def _edit_distance(self, dataset, logits, target, target_lens, lengths=None, ops=False, encoder=None):
         """ctc.edit_distance of the ids _metric decodes -- the greedy ids of every frame with <pad> / <blank> stripped
         and no repeat collapse (hp.beam_size 0), else the best beam hypothesis -- against the target ids, over the
         first min(rows of logits, rows of target) rows (the filter of _word_lists).  Nothing is read back.  The
-        hypothesis rows are as wide as the logits have frames: more than 1024 frames raise (ctc.EDIT_MAX_LEN)."""
+        hypothesis rows are as wide as the logits have frames: more than 1024 frames raise (ctc.EDIT_MAX_LEN).
+        encoder (hp.transducer_decode): the ids of _transducer_tokens instead."""
         voc = dataset.vocab
-        if getattr(self.hp, "beam_size", 0) > 0:
+        if encoder is not None:
+            toks, cnt = self._transducer_tokens(encoder, lengths)
+        elif getattr(self.hp, "beam_size", 0) > 0:
             _, _, toks, cnt = self._beam_search(voc, logits, lengths)
             toks, cnt = toks[:, 0], cnt[:, 0]
         else:
@@ -260,6 +305,7 @@ class Runner:
         if rnnt_weight is not None and not hasattr(self.model, "transducer"):
             raise ValueError("hp.transducer_weight is set but the model has no transducer head: call "
                              "HParams.set_transducer before the model is built")
+        rnnt_decode = self._transducer_decode_on()     # the metric from the transducer head (set_transducer_decode)
         for _ in range(epochs):
             self.model.train()
             train_set.shuffle(dataset_type)
@@ -274,7 +320,8 @@ class Runner:
                 inbatch, input_lens = batch["input"]["mels"], batch["input"]["tau"]
                 target, target_lens = batch["target"]["transcripts"], batch["target"]["lens"]
                 self.optimizer.zero_grad()
-                if rnnt_weight is not None:
+                encoder = None
+                if rnnt_weight is not None or rnnt_decode:
                     logits, output_lengths, encoder = self.model(inbatch, input_lens, SpecAugment,
                                                                  finetuning=finetuning, return_encoder=True)
                 else:
@@ -295,8 +342,8 @@ class Runner:
                     objective.backward()
                     self.optimizer.step()
                     with torch.no_grad():
-                        ed = self._edit_distance(train_set, logits.detach(), target, target_lens,
-                                                 output_lengths) if want_wer else None
+                        ed = self._edit_distance(train_set, logits.detach(), target, target_lens, output_lengths,
+                                                 encoder=encoder if rnnt_decode else None) if want_wer else None
                         self._accumulate(acc, ed, loss)
                     continue
                 cur = loss.item()
@@ -304,7 +351,8 @@ class Runner:
                 self.optimizer.step()
                 eloss.append(cur)
                 if want_wer:
-                    emetric.append(self._metric(train_set, logits.detach(), target, output_lengths))
+                    emetric.append(self._metric(train_set, logits.detach(), target, output_lengths,
+                                                encoder=encoder if rnnt_decode else None))
             self._check_device_errors()
             if device_wer:
                 eloss, emetric = self._read_accumulator(acc, train_size)
@@ -328,6 +376,7 @@ class Runner:
     def test(self, test_set, dataset_type="test", heatmap=False, finetuning=False):
         """runner.py:183-252 -> (mean loss, mean WER %); with hp.device_wer (mean loss, corpus WER %).  heatmap: the
         split's confusion matrix on self.confusion[dataset_type] and in hp.plots_dir (see the module docstring)."""
+        rnnt_decode = self._transducer_decode_on()
         self.model.eval()
         n = ceil(len(test_set.idxes[dataset_type]) / self.hp.batch_size)
         eloss, emetric = [], []
@@ -339,12 +388,18 @@ class Runner:
                 batch = test_set.get_batch(i, dataset_type)
                 inbatch, input_lens = batch["input"]["mels"], batch["input"]["tau"]
                 target, target_lens = batch["target"]["transcripts"], batch["target"]["lens"]
-                logits, output_lens = self.model(inbatch, input_lens, finetuning=finetuning)
+                encoder = None
+                if rnnt_decode:
+                    logits, output_lens, encoder = self.model(inbatch, input_lens, finetuning=finetuning,
+                                                              return_encoder=True)
+                else:
+                    logits, output_lens = self.model(inbatch, input_lens, finetuning=finetuning)
                 output_lens = nn.functional.pad(output_lens, (0, self.hp.batch_size - output_lens.shape[0]))
                 output_lens = output_lens.clamp(max=logits.shape[1])
                 loss = self.loss(logits.transpose(0, 1), target, output_lens, target_lens)
                 if heatmap or device_wer:
-                    ed = self._edit_distance(test_set, logits, target, target_lens, output_lens, ops=heatmap)
+                    ed = self._edit_distance(test_set, logits, target, target_lens, output_lens, ops=heatmap,
+                                             encoder=encoder)
                 if heatmap:
                     V = logits.shape[-1]
                     if conf is None:
@@ -354,7 +409,7 @@ class Runner:
                     self._accumulate(acc, ed, loss)
                     continue
                 eloss.append(loss.item())
-                emetric.append(self._metric(test_set, logits, target, output_lens))
+                emetric.append(self._metric(test_set, logits, target, output_lens, encoder=encoder))
         self._check_device_errors()
         if conf is not None:
             self._write_confusion(test_set, dataset_type, conf)
@@ -367,6 +422,7 @@ class Runner:
     def generate_labels(self, dataset):
         """runner.py:253-281: pseudo-labels for every clip of dataset's 'pretrain' split, in order.  With
         hp.nst_min_confidence set, a label whose confidence (Runner._confidence) is below it is None."""
+        rnnt_decode = self._transducer_decode_on()
         if getattr(self.hp, "nst_min_confidence", None) is not None and getattr(self.hp, "beam_size", 0) <= 0:
             raise ValueError("hp.nst_min_confidence needs hp.beam_size > 0: the greedy label path does not collapse "
                              "repeated frames (Vocab.decode, the reference's rule), so its labels generally have no "
@@ -381,6 +437,10 @@ class Runner:
         with torch.no_grad():
             for i in range(rank, n, world):
                 batch = dataset.get_batch(i, "pretrain")["input"]
+                if rnnt_decode:     # the transducer head's hypothesis, nothing from the CTC head
+                    _, out_lens, encoder = self.model(batch["mels"], batch["tau"], return_encoder=True)
+                    mine[i] = voc.decode(*self._transducer_tokens(encoder, out_lens))
+                    continue
                 logits, out_lens = self.model(batch["mels"], batch["tau"])
                 if getattr(self.hp, "beam_size", 0) > 0:
                     mine[i] = self._beam_labels(voc, logits, out_lens, confidence=True)

@@ -1203,6 +1203,23 @@ def rnnt_loss_bwd(x, targets_i32, ldt, in_len_i32, tgt_len_i32, blank, ws, grad_
     return g
 
 
+def rnnt_greedy(ep, gtab, w_hh, w_pp, b_pp, w_out, b_out, lengths_i32, blank, max_symbols, width):
+    """Transducer greedy search (cfm_rnnt_greedy) on fp32 contiguous device tensors: ep (B, T, J), gtab (V, 4H), w_hh
+    (4H, H), w_pp (J, H), b_pp (J), w_out (V, J), b_out (V); lengths_i32 (B,) int32 or None.
+    -> (tokens (B, width) int32 padded with -1, frames (B, width) int32, counts (B,) int32, scores (B,) fp32)."""
+    B, T, J = ep.shape
+    V, H = w_out.shape[0], w_hh.shape[1]
+    dev = ep.device
+    tokens = torch.empty(B, width, device=dev, dtype=torch.int32)
+    frames = torch.empty(B, width, device=dev, dtype=torch.int32)
+    counts = torch.empty(B, device=dev, dtype=torch.int32)
+    scores = torch.empty(B, device=dev, dtype=torch.float32)
+    L.call("cfm_rnnt_greedy", L.ptr(ep), L.ptr(gtab), L.ptr(w_hh), L.ptr(w_pp), L.ptr(b_pp), L.ptr(w_out),
+           L.ptr(b_out), L.ptr(lengths_i32), B, T, V, H, J, int(blank), int(max_symbols), int(width), L.ptr(tokens),
+           L.ptr(frames), L.ptr(counts), L.ptr(scores), L.stream())
+    return tokens, frames, counts, scores
+
+
 def edit_distance(ref_i32, ldr, ref_len_i32, hyp_i32, ldh, hyp_len_i32, P, group, rmax, hmax, want_ops=False,
                   out=None):
     """Batched edit distance over token ids (cfm_edit_distance): pair p compares hypothesis row p (hyp_i32 + p * ldh)

@@ -3,12 +3,17 @@
   rnnt_loss        the transducer loss of dense joint logits (B, T, U + 1, V), the interface of
                    torchaudio.functional.rnnt_loss: csrc/rnnt.hip (cfm_rnnt_loss_fwd / _bwd) behind an autograd function.
   TransducerHead   prediction network (Embedding -> lstm.LSTM per utterance) + joint network + rnnt_loss on an encoder
-                   output, with a time-synchronous greedy decode.
+                   output, with a time-synchronous greedy decode: decode (one kernel launch) and greedy_decode (the
+                   same search restated as a loop of torch ops).
+  rnnt_greedy_decode   that search on the head's weights as arrays: csrc/rnnt_greedy.hip (cfm_rnnt_greedy).
 
-The loss is the hot path and runs on HIP kernels; the joint network is plain torch ops (see TransducerHead).  Nothing
+The loss and the decode are the hot paths and run on HIP kernels; the joint network is plain torch ops (see
+TransducerHead).  Nothing
 here reads a device value back: lengths given as device tensors are clamped by the kernels.
 """
 from __future__ import annotations
+
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -101,6 +106,51 @@ class RNNTLoss(nn.Module):
     def forward(self, logits, targets, logit_lengths=None, target_lengths=None):
         return rnnt_loss(logits, targets, logit_lengths, target_lengths, self.blank, self.reduction,
                          self.zero_infinity)
+
+
+RNNTGreedy = namedtuple("RNNTGreedy", "tokens counts frames scores")
+
+
+def rnnt_greedy_decode(ep, gtab, w_hh, w_pp, b_pp, w_out, b_out, lengths=None, blank=0, max_symbols=2,
+                       max_tokens=None):
+    """Time-synchronous greedy search of a transducer head on the device, one launch (cfm_rnnt_greedy).
+
+    ep (B, T, J) = enc_proj(enc) with bias; gtab (V, 4H) = embedding.weight @ W_ih^T + b_ih + b_hh; w_hh (4H, H);
+    w_pp (J, H), b_pp (J): pred_proj; w_out (V, J), b_out (V): out.  CUDA floating-point tensors (cast to fp32, made
+    contiguous).  lengths: device tensor (clamped on the device to [0, T], never read back), host list (validated,
+    ValueError) or None (T).  H a multiple of 8, H and J at most 1024.
+    -> RNNTGreedy(tokens (B, W) int32 padded with -1, counts (B,) int32, frames (B, W) int32 padded with -1: the frame
+    each token was emitted at, scores (B,) fp32: the sum of log_softmax(logits)[chosen] over every decision taken --
+    labels and the blanks that close a frame; a frame closed by the max_symbols cap adds no blank term).
+    W = max_tokens or T * max_symbols; an utterance that has emitted W tokens stops there.  Ties of the argmax go to
+    the lowest index (torch's rule).  No host synchronisation; two runs are bit-identical."""
+    ts = (ep, gtab, w_hh, w_pp, b_pp, w_out, b_out)
+    if not all(torch.is_tensor(t) and t.is_cuda and t.is_floating_point() for t in ts):
+        raise RuntimeError("rnnt_greedy_decode runs on libcfm: floating-point CUDA tensors required")
+    if ep.dim() != 3 or w_out.dim() != 2 or w_hh.dim() != 2 or w_pp.dim() != 2 or gtab.dim() != 2:
+        raise ValueError("ep must be (B, T, J), gtab (V, 4H), w_hh (4H, H), w_pp (J, H), w_out (V, J)")
+    B, T, J = ep.shape
+    V, H = w_out.shape[0], w_hh.shape[1]
+    if min(B, T, J, H) < 1 or V < 2:
+        raise ValueError(f"need B, T, J, H >= 1 and V >= 2, got B {B}, T {T}, J {J}, H {H}, V {V}")
+    shapes = {"gtab": (gtab, (V, 4 * H)), "w_hh": (w_hh, (4 * H, H)), "w_pp": (w_pp, (J, H)), "b_pp": (b_pp, (J,)),
+              "w_out": (w_out, (V, J)), "b_out": (b_out, (V,))}
+    for name, (t, shape) in shapes.items():
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    blank, max_symbols = int(blank), int(max_symbols)
+    _check_blank(blank, V)
+    if max_symbols < 1:
+        raise ValueError("max_symbols must be >= 1")
+    W = T * max_symbols if max_tokens is None else int(max_tokens)
+    if W < 1:
+        raise ValueError("max_tokens must be >= 1")
+    dev = ep.device
+    lens = None if lengths is None else _lengths(lengths, B, dev, T, "lengths")
+    ep, gtab, w_hh, w_pp, b_pp, w_out, b_out = (t.to(device=dev, dtype=torch.float32).contiguous() for t in ts)
+    tokens, frames, counts, scores = ops.rnnt_greedy(ep, gtab, w_hh, w_pp, b_pp, w_out, b_out, lens, blank,
+                                                     max_symbols, W)
+    return RNNTGreedy(tokens, counts, frames, scores)
 
 
 class TransducerHead(nn.Module):
@@ -216,3 +266,19 @@ class TransducerHead(nn.Module):
                 c = torch.where(emit.unsqueeze(1), c2, c)
                 open_ = emit                                              # a blank closes the frame
         return tokens, counts.to(torch.int32)
+
+    @torch.no_grad()
+    def decode(self, enc, enc_lengths=None, max_symbols=2, max_tokens=None):
+        """greedy_decode's search as one kernel launch (rnnt_greedy_decode: real data-dependent control flow on the
+        device, a blank ends the frame's work) -> RNNTGreedy(tokens (B, W) int32 padded with -1, counts, frames,
+        scores), W = max_tokens or T * max_symbols.  enc_proj(enc) and the cell's input table embedding.weight @
+        W_ih^T + biases are one GEMM each per call; nothing is read back.  enc_lengths: device tensor, host list or
+        None (T)."""
+        p = self.prediction
+        gtab = self.embedding.weight.float() @ p.weight_ih_l0.float().t()
+        if p.bias:
+            gtab = gtab + (p.bias_ih_l0 + p.bias_hh_l0).float()
+        ep = self.enc_proj(enc.float())
+        return rnnt_greedy_decode(ep, gtab, p.weight_hh_l0, self.pred_proj.weight, self.pred_proj.bias,
+                                  self.out.weight, self.out.bias, enc_lengths, blank=self.blank,
+                                  max_symbols=max_symbols, max_tokens=max_tokens)
